@@ -15,9 +15,16 @@ N GPUs: each rank computes its partial (A_k, B_k) over its shard, partials are a
 over RCCL (torch.distributed 'nccl' backend) and every rank runs the pairing check; each rank
 keeps `--slots` global batches in flight (kzgmi.distributed.ShardedPipeline).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the
-dominant kernel (bucket accumulation) and `cpu_baseline` (the C oracle, timed on a bounded
-sample on this host's cores).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up,
+`--warmup` steps, `--steps` timed steps, the line.  `--full` adds every other leg (repeats, latencies, the other configs, MSM rates, the CPU verifiers, the
+default-queue child run) and with them `roofline` for the dominant kernel (bucket
+accumulation), `cpu_baseline` (the C oracle, timed on a bounded sample on this host's cores),
+`secondary` and `headline`.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32): `verdict` (1 = batch accepted) and, on the unsharded path, `combination_A` /
+`combination_B`, the bytes of the two combined G1 points the pairing check consumed.  Inputs
+and randomisers are seeded, so two builds run with the same arguments must agree byte for byte.
 """
 import argparse
 import hashlib
@@ -297,6 +304,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=24)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (all the *-steps options below, the CPU baseline, the "
+                         "roofline, the detail file); without it only the headline's warm-up and timed steps run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (verdict, combined points) as DIR/<name>.npy")
     ap.add_argument("--n", type=int, default=1 << 20, help="tuples per GPU")
     ap.add_argument("--curve", default="bls12_381", choices=["bls12_381", "bn254"])
     ap.add_argument("--slots", type=int, default=0,
@@ -340,6 +352,7 @@ def main():
                     help="sharded runs: batches of the strong-scaled leg (one --n batch split over the ranks; "
                          "default = --steps)")
     args = ap.parse_args()
+    full = args.full
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -394,6 +407,7 @@ def main():
             assert ok, "batch rejected"
 
     pending = [False] * slots
+    newest = [None]  # slot of the latest step_single
 
     def step_single(k):
         s = k % slots
@@ -401,16 +415,25 @@ def main():
             assert ctx.wait(s), "batch rejected"
         ctx.batch_verify_async(srs, s, Cm, z, y, P, n, seed=vseed)
         pending[s] = True
+        newest[0] = s
 
     def drain():
+        """Collect every batch in flight, each verdict asserted; returns the newest batch's verdict
+        (the step before the drain ran on slot `newest`), None if nothing was in flight."""
+        last = None
         if pipe is not None:
-            for ok in pipe.drain():
+            for ok in pipe.drain():  # oldest first
                 assert ok, "batch rejected"
-            return
+                last = ok
+            return last
         for s in range(slots):
             if pending[s]:
-                assert ctx.wait(s), "batch rejected"
+                ok = ctx.wait(s)
+                assert ok, "batch rejected"
                 pending[s] = False
+                if s == newest[0]:
+                    last = ok
+        return last
 
     def barrier():
         if world > 1:
@@ -434,7 +457,7 @@ def main():
             step_sharded()
         else:
             step_single(k)
-    drain()
+    last_verdict = drain()
     barrier()
     elapsed = time.perf_counter() - t0
     allocs_timed = kzgmi.alloc_count() - allocs0
@@ -446,10 +469,24 @@ def main():
         elapsed = float(t.item())
     value = world * args.steps / elapsed
 
+    # ---- what the last timed step gave its caller (--dump-outputs): the verdict, and the combined
+    # points (A, B) behind it.  kzgmi_last_combination reads slot 0, whose latest batch is one of
+    # the timed steps; every step verifies the same tuples with the same randomisers, so that
+    # pair is the last step's too.  Before any other leg, so nothing else has run on the slots.
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = {"verdict": np.array([float(bool(last_verdict))], dtype=np.float32)}
+        if not sharded and args.steps > 0:
+            for name, enc in zip(("combination_A", "combination_B"), ctx.last_combination(curve)):
+                dumped[name] = np.frombuffer(enc, dtype=np.uint8).astype(np.float32)
+        for name, arr in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+
     # ---- the same timed region repeated (median of >= 10 runs): value above is the
     # first run, as the contract asks; rep_values holds it and args.repeats - 1 more
     rep_values = [value]
-    for _ in range(args.repeats - 1):
+    for _ in range(args.repeats - 1 if full else 0):
         barrier()
         a = time.perf_counter()
         for k in range(args.steps):
@@ -470,7 +507,7 @@ def main():
     lat = None
     phases_single = phases_single_split = None
     lat_runs = None
-    if world == 1:
+    if full and world == 1:
         ts = []
         for _ in range(10):  # median of >= 10 runs
             torch.cuda.synchronize()
@@ -498,7 +535,7 @@ def main():
     # ---- configs[0] (BASELINE.json:7): a 256-tuple batch (the CPU verifier's time is added by
     # cpu_baseline below); GPU latency of the same batch, median of 10 synchronous calls
     cfg0 = None
-    if world == 1 and not sharded and n >= 256:
+    if full and world == 1 and not sharded and n >= 256:
         ts = []
         for _ in range(10):
             torch.cuda.synchronize()
@@ -515,7 +552,7 @@ def main():
     # split n/world per rank (shard_range), `slots` global batches in flight -- the per-rank
     # fixed costs (bucket reduction, window combination, pairing) do not shrink with the shard
     strong = None
-    if sharded:
+    if full and sharded:
         from kzgmi.distributed import shard_range
         off_s, n_s = shard_range(n, world, rank)
         g1b = 2 * kzgmi.FP_BYTES[curve]
@@ -552,7 +589,7 @@ def main():
 
     # ---- secondary: compressed inputs + subgroup checks, single GPU
     comp = None
-    if world == 1 and not sharded and args.compressed_steps > 0:
+    if full and world == 1 and not sharded and args.compressed_steps > 0:
         fb = kzgmi.FP_BYTES[curve]
         cc = torch.empty(n * fb, dtype=torch.uint8, device="cuda")
         pp = torch.empty(n * fb, dtype=torch.uint8, device="cuda")
@@ -592,7 +629,7 @@ def main():
     # ---- secondary: inputs declared G1 members (KZGMI_FLAG_TRUSTED_G1): the GLV split of s_i, t
     #  becomes exact on BLS12-381 and is used; single GPU
     trusted = None
-    if world == 1 and not sharded and args.trusted_steps > 0:
+    if full and world == 1 and not sharded and args.trusted_steps > 0:
         def tstep(k):
             s = k % slots
             if pending[s]:
@@ -620,7 +657,7 @@ def main():
 
     # ---- secondary: Fiat-Shamir randomisers, single GPU
     fsm = None
-    if world == 1 and not sharded and args.fs_steps > 0:
+    if full and world == 1 and not sharded and args.fs_steps > 0:
         def fstep(k):
             s = k % slots
             if pending[s]:
@@ -650,7 +687,7 @@ def main():
     # ---- secondary: prover-side fixed-base commit, single GPU,
     # pipelined over the slots like the batches (kzgmi_commit_device_async)
     commit = None
-    if world == 1 and not sharded and args.commit_steps > 0:
+    if full and world == 1 and not sharded and args.commit_steps > 0:
         a = time.perf_counter()
         ck = ctx.load_commit_key(curve, Cm.cpu().numpy().tobytes(), n)  # n points as a stand-in SRS
         load_s = time.perf_counter() - a
@@ -689,7 +726,7 @@ def main():
     # (kzgmi_host_alloc) is DMA'd directly; pageable numpy arrays go through the slots' pinned
     # staging rings (host copy by the library's copy pool).
     h2d = None
-    if world == 1 and not sharded and args.h2d_steps > 0:
+    if full and world == 1 and not sharded and args.h2d_steps > 0:
         g1b = 2 * kzgmi.FP_BYTES[curve]
         host_np = [t.cpu().numpy() for t in (Cm, z, y, P)]
         batch_bytes = sum(a.nbytes for a in host_np)
@@ -761,7 +798,7 @@ def main():
     # multi-GPU path (ShardedPipeline: partial + RCCL all-gather + combine per batch) and
     # unsharded; their ratio to `value` projects the 8-GPU strong speed-up of one 2^20 batch
     shard17 = None
-    if world == 1 and not sharded and args.shard17_steps > 0 and n >= (1 << 17):
+    if full and world == 1 and not sharded and args.shard17_steps > 0 and n >= (1 << 17):
         n17 = 1 << 17
         g1b = 2 * kzgmi.FP_BYTES[curve]
         v17 = (Cm[: n17 * g1b], z[: n17 * 32], y[: n17 * 32], P[: n17 * g1b])
@@ -806,7 +843,7 @@ def main():
     # ---- secondary: configs[4] (BASELINE.json:11) on one GPU: BN254 batches at the 8-GPU run's
     # per-GPU shard (2^19 tuples) and whole (2^22), pipelined over the slots, GLV (cofactor 1)
     bn = None
-    if world == 1 and not sharded and args.bn254_steps > 0 and curve == "bls12_381":
+    if full and world == 1 and not sharded and args.bn254_steps > 0 and curve == "bls12_381":
         bn = {}
         g2b = kzgmi.G2_GENERATOR["bn254"]
         tg2b = ctx.g2_mul("bn254", g2b, TAU % (1 << 250))
@@ -892,7 +929,7 @@ def main():
         return world * n * steps / dt, latency_ms, msm_ref
 
     msm_rate = msm_latency_ms = msm_rate_t = msm_latency_t = None
-    if args.msm_steps > 0:
+    if full and args.msm_steps > 0:
         msm_rate, msm_latency_ms, ref_u = msm_run(args.msm_steps)
         ctx.set_trusted_g1(True)
         msm_rate_t, msm_latency_t, ref_t = msm_run(args.msm_steps)
@@ -903,7 +940,7 @@ def main():
     # (strong scaling: 2^21 per rank at 8 GPUs), partial sums all-gathered over RCCL; 2 MSMs in
     # flight per rank (each slot's workspace holds ~8 GB at 2^24 points)
     cfg4 = None
-    if args.cfg4_msms > 0 and curve == "bls12_381":
+    if full and args.cfg4_msms > 0 and curve == "bls12_381":
         off4, m4 = (rank * args.cfg4_n // world, (rank + 1) * args.cfg4_n // world - rank * args.cfg4_n // world)
         gen = torch.Generator(device="cuda").manual_seed(1000 + rank)
         k4 = torch.randint(0, 256, (m4, 32), dtype=torch.uint8, device="cuda", generator=gen)
@@ -1011,6 +1048,41 @@ def main():
     if rank != 0:
         dist.barrier()
         dist.destroy_process_group()
+        return
+
+    out = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "batch-verifies/s (n=%d tuples per GPU per batch)" % n,
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("Montgomery Fp, 381-bit modular integer (radix-2^29 limbs in the bucket accumulation)"
+                  if curve == "bls12_381" else "Montgomery Fp, 254-bit modular integer"),
+        "data": "synthetic: valid toy-tau KZG openings generated on the GPU (kzgmi_gen_tuples), HBM-resident",
+        "config": {
+            "workload": "batch_verify (configs[2]): n=%d %s tuples per GPU, two G1 MSMs + 2-pairing check" % (n, curve),
+            "curve": curve,
+            "tuples_per_gpu": n,
+            "global_batch": world * n,
+            "pipeline_slots": slots,
+            "parallelism": "point-range shards" + (", RCCL all_gather of partial sums" if sharded else ""),
+        },
+        "full": full,
+    }
+    if not full:
+        # the plain run: the headline alone, plus what its timed region measured along the way
+        out["allocs_in_timed_region"] = allocs_timed
+        out["phase_ms_avg_in_timed_region"] = {k: float("%.4g" % v) for k, v in phases.items() if v}
+        out["hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES")
+        print(json.dumps(out), flush=True)
+        if sharded:
+            dist.barrier()
+            dist.destroy_process_group()
         return
 
     # ---- roofline of the dominant kernel (bucket accumulation + fixup)
@@ -1249,28 +1321,7 @@ def main():
         "default_hw_queues_frac": g(dq, "frac_of_value"),
         "detail_file": os.path.relpath(detail_path, ROOT) if detail_path else None,
     }
-    out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "batch-verifies/s (n=%d tuples per GPU per batch)" % n,
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("Montgomery Fp, 381-bit modular integer (radix-2^29 limbs in the bucket accumulation)"
-                  if curve == "bls12_381" else "Montgomery Fp, 254-bit modular integer"),
-        "data": "synthetic: valid toy-tau KZG openings generated on the GPU (kzgmi_gen_tuples), HBM-resident",
-        "config": {
-            "workload": "batch_verify (configs[2]): n=%d %s tuples per GPU, two G1 MSMs + 2-pairing check" % (n, curve),
-            "curve": curve,
-            "tuples_per_gpu": n,
-            "global_batch": world * n,
-            "pipeline_slots": slots,
-            "parallelism": "point-range shards" + (", RCCL all_gather of partial sums" if sharded else ""),
-        },
+    out.update({
         "roofline": roof_out,
         "cpu_baseline": cpu_out,
         "secondary": sec,
@@ -1288,7 +1339,7 @@ def main():
             "gpu_vs_cpu": sec["gpu_vs_cpu"],
             "gpu_vs_cpu_full_host_extrapolated": sec["gpu_vs_cpu_full_host_extrapolated"],
         },
-    }
+    })
     print(json.dumps(out), flush=True)
     if sharded:
         dist.barrier()

@@ -66,7 +66,9 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
     results = {label: [] for label, _ in variants}
     extra = {label: {k: [] for k in args.key} for label, _ in variants}
-    bench_args = shlex.split(args.bench) + ([] if args.no_quiet else shlex.split(QUIET))
+    # bench.py runs its secondary legs only with --full: needed for --no-quiet and for --key fields
+    bench_args = (shlex.split(args.bench) + ([] if args.no_quiet else shlex.split(QUIET))
+                  + (["--full"] if args.no_quiet or args.key else []))
     for r in range(args.rounds):
         for label, env in variants:
             e = dict(os.environ, **env)

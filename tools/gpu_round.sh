@@ -9,6 +9,7 @@ timeout -k 10 900 python -u -m pytest tests -x -v -m gpu -p no:cacheprovider --t
 tail -3 gpurun_out/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { cat gpurun_out/smoke.log; exit 1; }
 cat gpurun_out/smoke.log
+BENCH_ARGS=${BENCH_ARGS:---full}  # every leg of the record; without --full bench.py times the headline alone
 timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -30 gpurun_out/bench.err; exit 1; }
 cat gpurun_out/bench.json
 if [ -n "${SHARDED:-}" ]; then
