@@ -62,9 +62,10 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * kzgmi_batch_verify_ex_async, the pinned-host helpers kzgmi_host_* and kzgmi_slot_signal were
  * added.  5: partial records carry their shard's error (KZGMI_ERR_SHARD; combines fail on a
  * marked record), kzgmi_stream_wait orders the slot's NEXT job, multi-device contexts pipeline
- * whole batches per device through the async entry points (kzgmi_slot_device).  A caller built
+ * whole batches per device through the async entry points (kzgmi_slot_device).  6: the EIP-4844
+ * blob entry points kzgmi_blob_*_device and kzgmi_verify_blob_batch* were added.  A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
-#define KZGMI_ABI_VERSION 5
+#define KZGMI_ABI_VERSION 6
 
 #define KZGMI_OK 0
 #define KZGMI_ERR_ARG (-1)
@@ -254,6 +255,43 @@ int kzgmi_fs_chunk_digests_device(kzgmi_ctx* ctx, kzgmi_curve curve, const void*
                                   uint64_t index_offset, uint32_t flags, void* d_out);
 int kzgmi_fs_challenge_from_digests_device(kzgmi_ctx* ctx, kzgmi_curve curve, const void* d_digests,
                                            size_t nchunks, uint64_t n_total, uint8_t* r_out);
+
+/* ---- EIP-4844 blob batches (Deneb polynomial-commitments verify_blob_kzg_proof_batch) -------
+ * BLS12-381 only (an SRS of another curve: KZGMI_ERR_ARG), domain size 4096.  A blob is 4096 x
+ * 32 B big-endian canonical Fr (an element >= r: KZGMI_ERR_SCALAR); commitments and proofs are
+ * 48 B ZCash compressed G1, always decoded with KZGMI_FLAG_COMPRESSED |
+ * KZGMI_FLAG_SUBGROUP_CHECK semantics and error codes.  Device arrays are 16-byte aligned.
+ *   z_i = int_be(SHA256("FSBLOBVERIFY_V1_" || be128(4096) || blob_i || C_i)) mod r
+ *   y_i = p_i(z_i), p_i given by its values blob_i[j] at dom[j] = w^rev12(j), w = 7^((r-1)/4096)
+ *   r   = int_be(SHA256("RCKZGBATCH___V1_" || be64(4096) || be64(n) ||
+ *                       (C_i || be32B(z_i) || be32B(y_i) || pi_i for each i))) mod r
+ *   verdict: the KZGMI_FLAG_POWERS check with r_i = r^i (r = 0 gives 1, 0, 0, ...); n == 0 accepts.
+ * (blob_to_kzg_commitment is kzgmi_commit over a commit key of the Lagrange-form SRS in
+ * bit-reversed order.)
+ * The three stages, synchronous on slot 0 -- d_zs_out / d_ys_out: n x 32 B; kzgmi_blob_eval_device
+ * takes any z < r, points of the domain included: */
+int kzgmi_blob_challenges_device(kzgmi_ctx* ctx, const void* d_blobs, const void* d_commitments48,
+                                 size_t n, void* d_zs_out);
+int kzgmi_blob_eval_device(kzgmi_ctx* ctx, const void* d_blobs, const void* d_zs, size_t n,
+                           void* d_ys_out);
+int kzgmi_blob_batch_challenge_device(kzgmi_ctx* ctx, const void* d_commitments48, const void* d_zs,
+                                      const void* d_ys, const void* d_proofs48, size_t n,
+                                      uint8_t r_out[32]);
+/* The whole verification: the three stages and the batch check chained on the slot's stream with
+ * no host round trip (z_i, y_i and the power table live in the slot's workspace, grown on first
+ * use).  Host buffers (staged on slot 0 like kzgmi_batch_verify: pinned ranges by DMA, pageable
+ * ones through the slot's ring), device buffers, and the pipelined device form, whose verdict
+ * kzgmi_slot_wait returns.  kzgmi_last_combination works after the synchronous forms.  On a
+ * multi-device context the whole batch runs on the slot's device. */
+int kzgmi_verify_blob_batch(kzgmi_ctx* ctx, const kzgmi_srs* srs, const uint8_t* blobs,
+                            const uint8_t* commitments48, const uint8_t* proofs48, size_t n,
+                            int* ok_out);
+int kzgmi_verify_blob_batch_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const void* d_blobs,
+                                   const void* d_commitments48, const void* d_proofs48, size_t n,
+                                   int* ok_out);
+int kzgmi_verify_blob_batch_device_async(kzgmi_ctx* ctx, const kzgmi_srs* srs, int slot,
+                                         const void* d_blobs, const void* d_commitments48,
+                                         const void* d_proofs48, size_t n);
 
 /* Validate n device-resident G1 encodings (flags: KZGMI_FLAG_COMPRESSED,
  * KZGMI_FLAG_SUBGROUP_CHECK): 0 if all are valid, else the first error class found. */

@@ -104,6 +104,7 @@ struct Slot {
   DevBuf accq;                                   // k_accumulate's work-queue counter (large calls)
   DevBuf crowd;                                  // k_fixup's list of crowded buckets (msm.hpp k_fixup_crowded)
   DevBuf fs_leaves, fs_tmp, fs_top, pow, chal;  // Fiat-Shamir / powers-of-r randomisers
+  DevBuf blob_z, blob_y;                         // blob batches: the derived z_i, y_i (n x 32 B each)
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -132,7 +133,7 @@ struct Slot {
     DevBuf* bufs[] = {&pts, &inf, &scal_r, &scal_s, &scal_t, &tpart, &cnt, &off, &coarse, &ent, &total, &sval, &skey,
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
-                      &acc29b, &cntb, &offb};
+                      &acc29b, &cntb, &offb, &blob_z, &blob_y};
     for (DevBuf* b : bufs) f(*b);
   }
 };
@@ -218,6 +219,11 @@ struct kzgmi_ctx {
   DevBuf table[2], table_base[2];
   bool table_ready[2] = {false, false};
   DevBuf lines_tmp, tmp;
+  // EIP-4844 blob front end (blob.hpp): the evaluation domain, built at the first blob call
+  DevBuf blob_table;
+  bool blob_table_ready = false;
+  // KZGMI_BLOB_HASH=lane|wave forces the blob hash's mapping (A/B, tools/bench_blobs.py); 0: blob_mapping()
+  int blob_hash = 0;
   DevBuf gath;                       // multi-device: partial records gathered from every device
   DevBuf mdig, mdig_all;             // multi-device Fiat-Shamir: this device's / every device's subtree roots
   std::vector<kzgmi_ctx*> peers;     // multi-device: contexts of device_ids[1..] (kzgmi_ctx_create, n_devices > 1)
@@ -690,11 +696,18 @@ int call_wbits(const kzgmi_ctx* c, size_t entries16, size_t max13) {
 inline uint32_t windows_half(int wb) { return (uint32_t)((128 + wb - 1) / wb); }
 inline uint32_t windows_full(int wb) { return (uint32_t)((256 + wb - 1) / wb); }
 
+// The blob hash's mapping (blob.hpp): a lane per blob at every n -- the wave-per-blob form lost
+// at n = 6, 64 and 4096 alike (profiles/blob/bench_blobs.md), so there is no crossover to switch on
+int blob_mapping(const kzgmi_ctx* c, size_t n) {
+  (void)n;
+  return c->blob_hash ? c->blob_hash : BlobLaunch::HASH_LANE;
+}
+
 // ------------------------------------------------------------------------------ batch
 template <class Cv>
 int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, const void* dz, const void* dy,
                   const void* dpi, size_t n, const Seed& seed, uint64_t offset, void* d_partial_out,
-                  uint32_t flags, bool dry = false) {
+                  uint32_t flags, bool dry = false, const void* d_blobs = nullptr) {
   using XY = Xyzz<Cv>;
   using FrF = Fp<typename Cv::FrP>;
   const bool glv = c->glv_batch &&
@@ -717,6 +730,14 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
   CHK(s.scal_t.ensure(32));
   CHK(s.tpart.ensure(L::tpart_bytes((uint32_t)n)));
   CHK(s.flags.ensure(16));
+  if (d_blobs) {  // blob batch (powers mode): z_i, y_i and r are derived on the device, in front()
+    CHK(s.blob_z.ensure(n * 32));
+    CHK(s.blob_y.ensure(n * 32));
+    CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
+    CHK(s.chal.ensure(32));
+    dz = s.blob_z.p;
+    dy = s.blob_y.p;
+  }
   if (dry) {  // kzgmi_ctx_reserve: the randomiser workspaces of this mode, no launches
     if (flags & KZGMI_FLAG_FIAT_SHAMIR) CHK(reserve_fs<Cv>(s, n));
     else if (flags & KZGMI_FLAG_POWERS) CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
@@ -762,6 +783,13 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
       const uint32_t* digests = nullptr;
       CHK(enqueue_fs_digests<Cv>(s, dC, dpi, dz, dy, n, 0, (flags & KZGMI_FLAG_COMPRESSED) != 0, &digests));
       CHK(enqueue_fs_challenge<Cv>(s, digests, (uint32_t)((n + FS_CHUNK - 1) / FS_CHUNK), n));
+    } else if (d_blobs) {  // the EIP-4844 transcript: z_i, y_i = p_i(z_i), then r and its power table
+      uint8_t* bz = s.blob_z.template as<uint8_t>();
+      uint8_t* by = s.blob_y.template as<uint8_t>();
+      BlobLaunch::challenges(st, blob_mapping(c, n), (const uint8_t*)d_blobs, (const uint8_t*)dC, (uint32_t)n, bz, err);
+      BlobLaunch::eval(st, (const uint8_t*)d_blobs, bz, c->blob_table.p, (uint32_t)n, false, by, err);
+      BlobLaunch::batch_challenge(st, (const uint8_t*)dC, bz, by, (const uint8_t*)dpi, (uint32_t)n, s.pow.p,
+                                  s.chal.template as<uint32_t>());
     } else if (flags & KZGMI_FLAG_POWERS) {  // r supplied by the caller in place of the seed
       CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
       L::pow_table(st, seed, s.pow.p, err);
@@ -1211,7 +1239,7 @@ int enqueue_batch_chunked(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const uin
 // ================================================================================ C ABI
 extern "C" {
 
-const char* kzgmi_version(void) { return "kzgmi 0.5 (abi " KZ_STR(KZGMI_ABI_VERSION) ", gfx950, HIP)"; }
+const char* kzgmi_version(void) { return "kzgmi 0.6 (abi " KZ_STR(KZGMI_ABI_VERSION) ", gfx950, HIP)"; }
 int kzgmi_abi_version(void) { return KZGMI_ABI_VERSION; }
 uint64_t kzgmi_alloc_count(void) { return g_allocs.load(std::memory_order_relaxed); }
 const char* kzgmi_last_error(void) { return g_err.c_str(); }
@@ -1245,6 +1273,8 @@ int kzgmi_ctx_create_device(kzgmi_ctx** out, int device_id, int pipeline_slots) 
   if (const char* e = getenv("KZGMI_SPLIT_SIDEFIX")) c->split_side_fix = atoi(e) != 0;
   if (const char* e = getenv("KZGMI_SPLIT_SIDEPRIO")) c->split_side_prio = atoi(e) != 0;
   if (const char* e = getenv("KZGMI_SPLIT_REV")) c->split_rev = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_BLOB_HASH"))
+    c->blob_hash = !strcmp(e, "lane") ? BlobLaunch::HASH_LANE : !strcmp(e, "wave") ? BlobLaunch::HASH_WAVE : 0;
   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless set before the runtime
   // starts) and serialises the streams of one queue, so every slot in flight needs a queue of its
   // own (16 slots on 24 queues pipeline; 24 on 24 ran 3.6x slower).  The runtime keeps that many
@@ -1330,6 +1360,7 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
 
   c->lines_tmp.release();
   c->tmp.release();
+  c->blob_table.release();
   for (kzgmi_ck* ck : c->ck_list) {  // detach: later kzgmi_ck_free() only deletes the struct
     ck->pts.release();
     ck->inf.release();
@@ -2247,6 +2278,151 @@ int kzgmi_fs_challenge_device(kzgmi_ctx* c, kzgmi_curve curve, const void* dC, c
       for (int b = 0; b < 4; ++b) r_out[4 * k + b] = (uint8_t)(w[k] >> (24 - 8 * b));
     return 0;
   });
+}
+
+// ------------------------------------------------------------------------------ EIP-4844 blobs
+}  // extern "C"
+namespace {
+constexpr size_t kBlobMax = size_t(1) << 20;  // blobs per call
+constexpr uint32_t kBlobFlags = KZGMI_FLAG_POWERS | KZGMI_FLAG_COMPRESSED | KZGMI_FLAG_SUBGROUP_CHECK;
+
+// the evaluation domain of this context's device, once (on st, waited for)
+int ensure_blob_table(kzgmi_ctx* c, hipStream_t st) {
+  if (c->blob_table_ready) return 0;
+  CHK(c->blob_table.ensure(BlobLaunch::table_bytes()));
+  BlobLaunch::domain(st, c->blob_table.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  c->blob_table_ready = true;
+  return 0;
+}
+
+// A synchronous utility job on slot 0 whose kernels report through the slot's error word
+template <class F>
+int blob_slot0_job(kzgmi_ctx* c, F&& launch) {
+  CHK(slot0_idle(c));
+  Slot& s = c->slots[0];
+  CHK(s.flags.ensure(16));
+  CHK(ensure_blob_table(c, s.stream));
+  CHK(begin_job(s));
+  HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, s.stream));
+  CHK(launch(s, s.flags.template as<uint32_t>() + 1));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, s.stream));
+  CHK(end_job(s));
+  s.pending = true;
+  s.partial_job = true;
+  s.msm_job = false;
+  return finish_slot(c, s, nullptr);
+}
+}  // namespace
+extern "C" {
+
+int kzgmi_blob_challenges_device(kzgmi_ctx* c, const void* d_blobs, const void* d_commitments48, size_t n,
+                                 void* d_zs_out) {
+  CHK(check_ctx(c));
+  if (n && (!d_blobs || !d_commitments48 || !d_zs_out)) return fail(KZGMI_ERR_ARG, "null argument");
+  if (n > kBlobMax) return fail(KZGMI_ERR_ARG, "too many blobs (max 2^20 per call)");
+  if (n == 0) return 0;
+  return blob_slot0_job(c, [&](Slot& s, uint32_t* err) -> int {
+    BlobLaunch::challenges(s.stream, blob_mapping(c, n), (const uint8_t*)d_blobs, (const uint8_t*)d_commitments48,
+                           (uint32_t)n, (uint8_t*)d_zs_out, err);
+    return 0;
+  });
+}
+
+int kzgmi_blob_eval_device(kzgmi_ctx* c, const void* d_blobs, const void* d_zs, size_t n, void* d_ys_out) {
+  CHK(check_ctx(c));
+  if (n && (!d_blobs || !d_zs || !d_ys_out)) return fail(KZGMI_ERR_ARG, "null argument");
+  if (n > kBlobMax) return fail(KZGMI_ERR_ARG, "too many blobs (max 2^20 per call)");
+  if (n == 0) return 0;
+  return blob_slot0_job(c, [&](Slot& s, uint32_t* err) -> int {
+    BlobLaunch::eval(s.stream, (const uint8_t*)d_blobs, (const uint8_t*)d_zs, c->blob_table.p, (uint32_t)n, true,
+                     (uint8_t*)d_ys_out, err);
+    return 0;
+  });
+}
+
+int kzgmi_blob_batch_challenge_device(kzgmi_ctx* c, const void* d_commitments48, const void* d_zs, const void* d_ys,
+                                      const void* d_proofs48, size_t n, uint8_t r_out[32]) {
+  CHK(check_ctx(c));
+  if (!r_out || (n && (!d_commitments48 || !d_zs || !d_ys || !d_proofs48))) return fail(KZGMI_ERR_ARG, "null argument");
+  if (n > kBlobMax) return fail(KZGMI_ERR_ARG, "too many blobs (max 2^20 per call)");
+  uint32_t w[8];
+  CHK(blob_slot0_job(c, [&](Slot& s, uint32_t*) -> int {
+    CHK(s.pow.ensure(FS_POW_BITS * sizeof(Fp<Bls12_381::FrP>)));
+    CHK(s.chal.ensure(32));
+    BlobLaunch::batch_challenge(s.stream, (const uint8_t*)d_commitments48, (const uint8_t*)d_zs, (const uint8_t*)d_ys,
+                                (const uint8_t*)d_proofs48, (uint32_t)n, s.pow.p, s.chal.template as<uint32_t>());
+    HIPCHK(hipMemcpyAsync(w, s.chal.p, 32, hipMemcpyDeviceToHost, s.stream));
+    return 0;
+  }));
+  for (int k = 0; k < 8; ++k)
+    for (int b = 0; b < 4; ++b) r_out[4 * k + b] = (uint8_t)(w[k] >> (24 - 8 * b));
+  return 0;
+}
+
+int kzgmi_verify_blob_batch_device_async(kzgmi_ctx* c, const kzgmi_srs* srs, int slot, const void* d_blobs,
+                                         const void* d_commitments48, const void* d_proofs48, size_t n) {
+  KZ_ROUTE(c, &srs, slot);
+  CHK(check_ctx(c, slot));
+  if (!srs || srs->ctx != c) return fail(KZGMI_ERR_ARG, "srs does not belong to this context");
+  if (srs->curve != 0) return fail(KZGMI_ERR_ARG, "blob verification is BLS12-381 only");
+  if (n && (!d_blobs || !d_commitments48 || !d_proofs48)) return fail(KZGMI_ERR_ARG, "null input");
+  if (n > kBlobMax) return fail(KZGMI_ERR_ARG, "too many blobs (max 2^20 per call)");
+  Slot& s = c->slots[slot];
+  if (s.pending) return fail(KZGMI_ERR_ARG, "slot busy: call kzgmi_slot_wait first");
+  if (n == 0) {  // accepts
+    CHK(sync_slot(s));  // host_flags may still be the target of a copy
+    s.host_flags[0] = 1;
+    s.host_flags[1] = 0;
+    s.pending = true;
+    s.partial_job = false;
+    s.partial_of = 0;
+    s.msm_job = false;
+    return 0;
+  }
+  Roctx rx("kzgmi_verify_blob_batch_device_async");
+  CHK(ensure_blob_table(c, s.stream));
+  return enqueue_batch<Bls12_381>(c, s, srs, d_commitments48, nullptr, nullptr, d_proofs48, n, Seed{}, 0, nullptr,
+                                  kBlobFlags, /*dry=*/false, d_blobs);
+}
+
+int kzgmi_verify_blob_batch_device(kzgmi_ctx* c, const kzgmi_srs* srs, const void* d_blobs,
+                                   const void* d_commitments48, const void* d_proofs48, size_t n, int* ok_out) {
+  if (!c) return fail(KZGMI_ERR_ARG, "null context");
+  if (!ok_out) return fail(KZGMI_ERR_ARG, "null ok_out");
+  c->sync_call = true;
+  const int rc = kzgmi_verify_blob_batch_device_async(c, srs, 0, d_blobs, d_commitments48, d_proofs48, n);
+  c->sync_call = false;
+  CHK(rc);
+  return kzgmi_slot_wait(c, 0, ok_out);
+}
+
+int kzgmi_verify_blob_batch(kzgmi_ctx* c, const kzgmi_srs* srs, const uint8_t* blobs, const uint8_t* commitments48,
+                            const uint8_t* proofs48, size_t n, int* ok_out) {
+  CHK(check_ctx(c));
+  if (!srs || !ok_out) return fail(KZGMI_ERR_ARG, "null argument");
+  if (srs->ctx != c) return fail(KZGMI_ERR_ARG, "srs does not belong to this context");
+  if (srs->curve != 0) return fail(KZGMI_ERR_ARG, "blob verification is BLS12-381 only");
+  if (n && (!blobs || !commitments48 || !proofs48)) return fail(KZGMI_ERR_ARG, "null input");
+  if (n > kBlobMax) return fail(KZGMI_ERR_ARG, "too many blobs (max 2^20 per call)");
+  CHK(slot0_idle(c));
+  Slot& s = c->slots[0];
+  uint8_t *dB = nullptr, *dC = nullptr, *dpi = nullptr;
+  if (n) {  // blobs, commitments, proofs into the slot's stage buffer on the FIFO copy stream
+    CHK(s.stage.ensure(n * (BlobLaunch::BYTES + 96)));
+    dB = s.stage.template as<uint8_t>();
+    dC = dB + n * BlobLaunch::BYTES;
+    dpi = dC + n * 48;
+    hipStream_t cs = c->h2d_stream;
+    if (s.done_rec) HIPCHK(hipStreamWaitEvent(cs, s.done_ev, 0));  // the stage buffer is free
+    CHK(h2d(s, cs, dB, blobs, n * BlobLaunch::BYTES));
+    CHK(h2d(s, cs, dC, commitments48, n * 48));
+    CHK(h2d(s, cs, dpi, proofs48, n * 48));
+    CHK(add_dep(s, cs));  // the batch's kernels wait for its copy only
+  }
+  return kzgmi_verify_blob_batch_device(c, srs, dB, dC, dpi, n, ok_out);
 }
 
 int kzgmi_g1_compress_device(kzgmi_ctx* c, kzgmi_curve curve, const void* d_points, size_t n, void* d_out) {

@@ -111,6 +111,24 @@ struct Launch {
                          uint8_t* cm, uint8_t* zs, uint8_t* ys, uint8_t* pf);
 };
 
+// ---- EIP-4844 blob front end (blob.hpp, launch_blob.hip): BLS12-381 only, 4096-element blobs
+struct BlobLaunch {
+  // the blob hash's mapping: a lane per blob, or a wave per blob on wave-uniform values
+  static constexpr int HASH_LANE = 1, HASH_WAVE = 2;
+  static constexpr size_t BYTES = 4096 * 32;        // one blob
+  static size_t table_bytes();                      // the domain table: dom[0 .. 4096), 4096^-1
+  static void domain(hipStream_t st, void* table);
+  // z_i = H(tag || blob_i || C_i) mod r -> zs (n x 32 B); every blob element range-checked
+  static void challenges(hipStream_t st, int mapping, const uint8_t* blobs, const uint8_t* commitments, uint32_t n,
+                         uint8_t* zs, uint32_t* err);
+  // y_i = p_i(z_i) -> ys; range_check: the blob elements are checked here (else they were already)
+  static void eval(hipStream_t st, const uint8_t* blobs, const uint8_t* zs, const void* table, uint32_t n,
+                   bool range_check, uint8_t* ys, uint32_t* err);
+  // r of the batch -> chal_out (8 big-endian words) and the power table of scalar_prep_pow
+  static void batch_challenge(hipStream_t st, const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys,
+                              const uint8_t* proofs, uint32_t n, void* pow, uint32_t* chal_out);
+};
+
 inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace kzgmi

@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # KZGMI_LIB selects an alternative build (timing experiments); default: the in-tree library
 LIB_PATH = os.environ.get("KZGMI_LIB") or os.path.join(_HERE, "libkzgmi.so")
 
-ABI_VERSION = 5  # include/kzgmi.h KZGMI_ABI_VERSION
+ABI_VERSION = 6  # include/kzgmi.h KZGMI_ABI_VERSION
 CURVES = {"bls12_381": 0, "bn254": 1}
 FP_BYTES = {"bls12_381": 48, "bn254": 32}
 PHASES = ["convert", "scalars", "sort", "accumulate", "reduce", "combine", "pairing", "h2d"]
@@ -96,6 +96,12 @@ def lib():
         "kzgmi_fs_challenge_device": ([vp, c.c_int, vp, vp, vp, vp, sz, c.c_uint32, u8p], c.c_int),
         "kzgmi_fs_chunk_digests_device": ([vp, c.c_int, vp, vp, vp, vp, sz, c.c_uint64, c.c_uint32, vp], c.c_int),
         "kzgmi_fs_challenge_from_digests_device": ([vp, c.c_int, vp, sz, c.c_uint64, u8p], c.c_int),
+        "kzgmi_blob_challenges_device": ([vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_blob_eval_device": ([vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_blob_batch_challenge_device": ([vp, vp, vp, vp, vp, sz, u8p], c.c_int),
+        "kzgmi_verify_blob_batch": ([vp, vp, vp, vp, vp, sz, ip], c.c_int),
+        "kzgmi_verify_blob_batch_device": ([vp, vp, vp, vp, vp, sz, ip], c.c_int),
+        "kzgmi_verify_blob_batch_device_async": ([vp, vp, c.c_int, vp, vp, vp, sz], c.c_int),
         "kzgmi_slot_wait": ([vp, c.c_int, ip], c.c_int),
         "kzgmi_last_combination": ([vp, u8p, u8p], c.c_int),
         "kzgmi_msm_g1": ([vp, c.c_int, vp, vp, sz, u8p], c.c_int),
@@ -154,6 +160,8 @@ def exported_symbols():
         "kzgmi_batch_verify_multi_device", "kzgmi_msm_g1_multi_device",
         "kzgmi_abi_version", "kzgmi_ctx_reserve", "kzgmi_alloc_count", "kzgmi_batch_verify_ex_async",
         "kzgmi_host_alloc", "kzgmi_host_free", "kzgmi_host_register", "kzgmi_host_unregister",
+        "kzgmi_blob_challenges_device", "kzgmi_blob_eval_device", "kzgmi_blob_batch_challenge_device",
+        "kzgmi_verify_blob_batch", "kzgmi_verify_blob_batch_device", "kzgmi_verify_blob_batch_device_async",
     ]
 
 
@@ -164,6 +172,7 @@ FLAG_FIAT_SHAMIR = 8
 FLAG_TRUSTED_G1 = 16
 ERR_NOT_IN_SUBGROUP = -7
 FS_CHUNK = 4096
+BLOB_BYTES = 4096 * 32  # an EIP-4844 blob: 4096 big-endian canonical Fr elements
 
 
 def _flags(compressed: bool = False, subgroup_check: bool = False, fiat_shamir: bool = False,
@@ -603,6 +612,65 @@ class Context:
         self._order(0)
         _check(lib().kzgmi_g1_compress_device(self.handle, CURVES[curve], pi, n, po))
 
+    # ------------------------------------------------------------------ EIP-4844 blobs
+    def blob_challenges(self, blobs, commitments, n: int, out=None):
+        """z_i = H("FSBLOBVERIFY_V1_" || be128(4096) || blob_i || C_i) mod r for n device-resident
+        blobs (n x 128 KiB) and compressed commitments (n x 48 B): a device tensor of n x 32 B."""
+        import torch
+        if out is None:
+            out = torch.empty(32 * n, dtype=torch.uint8, device=blobs.device)
+        pb, pc, po = _dptr(blobs, n * BLOB_BYTES), _dptr(commitments, 48 * n), _dptr(out, 32 * n)
+        self._order(0)
+        _check(lib().kzgmi_blob_challenges_device(self.handle, pb, pc, int(n), po))
+        return out
+
+    def blob_eval(self, blobs, zs, n: int, out=None):
+        """y_i = p_i(z_i) for the blob polynomials in evaluation form over the bit-reversed 4096th
+        roots of unity (any z < r, points of the domain included): a device tensor of n x 32 B."""
+        import torch
+        if out is None:
+            out = torch.empty(32 * n, dtype=torch.uint8, device=blobs.device)
+        pb, pz, po = _dptr(blobs, n * BLOB_BYTES), _dptr(zs, 32 * n), _dptr(out, 32 * n)
+        self._order(0)
+        _check(lib().kzgmi_blob_eval_device(self.handle, pb, pz, int(n), po))
+        return out
+
+    def blob_batch_challenge(self, commitments, zs, ys, proofs, n: int) -> int:
+        """r = H("RCKZGBATCH___V1_" || be64(4096) || be64(n) || (C_i || z_i || y_i || pi_i)_i) mod r
+        for device-resident arrays."""
+        out = ctypes.create_string_buffer(32)
+        ptrs = (_dptr(commitments, 48 * n), _dptr(zs, 32 * n), _dptr(ys, 32 * n), _dptr(proofs, 48 * n))
+        self._order(0)
+        _check(lib().kzgmi_blob_batch_challenge_device(self.handle, *ptrs, int(n), out))
+        return int.from_bytes(out.raw, "big")
+
+    def verify_blob_batch(self, srs: Srs, blobs, commitments, proofs, n: Optional[int] = None) -> bool:
+        """verify_blob_kzg_proof_batch: blobs (n x 128 KiB), compressed commitments and proofs
+        (n x 48 B each) as host buffers or device tensors; challenges, evaluations and the
+        powers-of-r batch check all run on the GPU."""
+        ok = ctypes.c_int(-1)
+        if _is_device_tensor(blobs):
+            if n is None:
+                n = commitments.numel() // 48
+            ptrs = (_dptr(blobs, n * BLOB_BYTES), _dptr(commitments, 48 * n), _dptr(proofs, 48 * n))
+            self._order(0)
+            _check(lib().kzgmi_verify_blob_batch_device(self.handle, srs.handle, *ptrs, int(n), ctypes.byref(ok)))
+        else:
+            (pb, lb, kb), (pc, lc, kc), (pp, lp, kp) = (_host_ptr(v) for v in (blobs, commitments, proofs))
+            if n is None:
+                n = lc // 48
+            if lb < n * BLOB_BYTES or lc < 48 * n or lp < 48 * n:
+                raise ValueError("input buffers shorter than n blobs")
+            _check(lib().kzgmi_verify_blob_batch(self.handle, srs.handle, pb, pc, pp, int(n), ctypes.byref(ok)))
+            del kb, kc, kp
+        return bool(ok.value)
+
+    def verify_blob_batch_async(self, srs: Srs, slot: int, blobs, commitments, proofs, n: int):
+        """Enqueue verify_blob_batch of device tensors on `slot`; wait(slot) returns the verdict."""
+        ptrs = (_dptr(blobs, n * BLOB_BYTES), _dptr(commitments, 48 * n), _dptr(proofs, 48 * n))
+        self._order(slot)
+        _check(lib().kzgmi_verify_blob_batch_device_async(self.handle, srs.handle, int(slot), *ptrs, int(n)))
+
     def wait(self, slot: int) -> bool:
         ok = ctypes.c_int(-1)
         try:
@@ -826,6 +894,11 @@ def batch_verify(commitments, zs, ys, proofs, srs: Srs, seed: Optional[bytes] = 
     return srs.ctx.batch_verify(srs, commitments, zs, ys, proofs, seed=seed, compressed=compressed,
                                 subgroup_check=subgroup_check, fiat_shamir=fiat_shamir, challenge=challenge,
                                 trusted_g1=trusted_g1)
+
+
+def verify_blob_batch(blobs, commitments, proofs, srs: Srs, n: Optional[int] = None) -> bool:
+    """EIP-4844 verify_blob_kzg_proof_batch(blobs, commitments, proofs) on the GPU (BLS12-381)."""
+    return srs.ctx.verify_blob_batch(srs, blobs, commitments, proofs, n=n)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:

@@ -196,6 +196,17 @@ def window_steps(e, w=4):
     return first, steps
 
 
+BLOB_DOMAIN = 4096  # FIELD_ELEMENTS_PER_BLOB of EIP-4844
+
+
+def blob_root(r):
+    """The primitive 4096th root of unity 7^((r-1)/4096) mod r of the EIP-4844 evaluation domain."""
+    assert (r - 1) % BLOB_DOMAIN == 0
+    w = pow(7, (r - 1) // BLOB_DOMAIN, r)
+    assert pow(w, BLOB_DOMAIN, r) == 1 and pow(w, BLOB_DOMAIN // 2, r) == r - 1
+    return w
+
+
 def main():
     out = ["// GENERATED by tools/gen_params.py -- do not edit.",
            "// 32-bit little-endian limbs; *_M = Montgomery form (R = 2^(32*N)).",
@@ -235,6 +246,9 @@ def main():
         out.append("  static constexpr uint32_t R2[N] = %s;" % arr(Rr * Rr % r, 8))
         out.append("  static constexpr uint32_t INV = 0x%08xu;" % ((-pow(r, -1, 1 << 32)) % (1 << 32)))
         out.append("  static constexpr uint32_t PM2[N] = %s;" % arr(r - 2, 8))
+        if name == "Bls12_381":  # EIP-4844 blob domain (blob.hpp): omega = 7^((r-1)/4096), order 4096
+            w = blob_root(r)
+            out.append("  static constexpr uint32_t ROOT4096_M[N] = %s;  // 7^((r-1)/4096), Montgomery" % arr(w * Rr % r, 8))
         out.append("};")
         xi = c["xi"]
         if c["twist"] == "M":
