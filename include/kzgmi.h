@@ -63,7 +63,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * added.  5: partial records carry their shard's error (KZGMI_ERR_SHARD; combines fail on a
  * marked record), kzgmi_stream_wait orders the slot's NEXT job, multi-device contexts pipeline
  * whole batches per device through the async entry points (kzgmi_slot_device).  6: the EIP-4844
- * blob entry points kzgmi_blob_*_device and kzgmi_verify_blob_batch* were added.  A caller built
+ * blob entry points kzgmi_blob_*_device and kzgmi_verify_blob_batch* were added; still 6 (additive):
+ * the EIP-7594 cell entry points kzgmi_cell_* and kzgmi_verify_cell_batch*.  A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
 
@@ -292,6 +293,58 @@ int kzgmi_verify_blob_batch_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const v
 int kzgmi_verify_blob_batch_device_async(kzgmi_ctx* ctx, const kzgmi_srs* srs, int slot,
                                          const void* d_blobs, const void* d_commitments48,
                                          const void* d_proofs48, size_t n);
+
+/* ---- EIP-7594 cell batches (PeerDAS polynomial-commitments-sampling verify_cell_kzg_proof_batch) --
+ * BLS12-381 only.  r is the scalar modulus, w = 7^((r-1)/8192) (its square is the blob domain's
+ * root), rev_b is b-bit reversal.  A cell is 64 x 32 B big-endian canonical Fr, 2048 B (an element
+ * >= r: KZGMI_ERR_SCALAR).  Element j of a cell with cell_index i (0 <= i < 128) is the polynomial's
+ * value at w^rev13(64 i + j) = h_i * w64^rev6(j), with h_i = w^rev7(i) and w64 = w^128; so
+ * h_i^64 = (w^64)^rev7(i).  The cell's interpolation polynomial I = p mod (X^64 - h_i^64) is
+ *   I(X) = sum_m c_m X^m,  c_m = h_i^-m * 64^-1 * sum_j e_j * w64^(-rev6(j) m).
+ * Inputs are deduplicated: commitments48[m] are unique 48 B compressed commitments,
+ * commitment_indices[n] and cell_indices[n] are uint64 (little-endian in memory), cells[n] are
+ * 2048 B each, proofs48[n] 48 B compressed; commitments and proofs are decoded with
+ * KZGMI_FLAG_COMPRESSED | KZGMI_FLAG_SUBGROUP_CHECK semantics and error codes.  Device arrays are
+ * 16-byte aligned.  cell_index >= 128 or commitment_index >= m: KZGMI_ERR_ARG (found on the
+ * device).  Duplicate (commitment, cell) pairs are legal; n == 0 accepts.
+ *   r = int_be(SHA256("RCKZGCBATCH__V1_" || be64(4096) || be64(64) || be64(m) || be64(n)
+ *         || C_0 .. C_{m-1}
+ *         || for k < n: be64(commitment_indices[k]) || be64(cell_indices[k]) || cells[k] || proofs[k]))
+ *       mod r                                           (48 + 48 m + 2112 n message bytes)
+ *   verdict: e(sum r^k pi_k, [tau^64]_2) = e(sum r^k C_k + sum r^k h_k^64 pi_k - [sum r^k I_k(tau)]_1, [1]_2)
+ *   with weights r^k, k = 0 .. n-1 (r = 0 gives 1, 0, 0, ...).
+ * The transcript hash is one sequential SHA-256 (33 compressions per cell), so every verify entry
+ * point takes an optional caller-supplied r32 (32 B big-endian, < r): NULL derives r on the device;
+ * a caller holding the bytes on the host can hash there.
+ * The cell SRS: g1_monomial = [tau^m]_1 for m < 64 (64 x 96 B uncompressed, all validated and in
+ * G1), [1]_2 and [tau^64]_2.  It holds an ordinary kzgmi_srs for ([tau^0]_1, [1]_2, [tau^64]_2).
+ * Passing anything else where a kzgmi_cell_srs is expected: KZGMI_ERR_ARG. */
+typedef struct kzgmi_cell_srs kzgmi_cell_srs;
+int kzgmi_cell_srs_load(kzgmi_ctx* ctx, const uint8_t* g1_monomial, const uint8_t* g2, const uint8_t* tau64_g2,
+                        kzgmi_cell_srs** out);
+void kzgmi_cell_srs_free(kzgmi_cell_srs* srs);
+/* The stages, synchronous on slot 0.  kzgmi_cell_interp_device: the aggregated coefficients c_m of
+ * sum_k r^k I_k for the given r32 (required) -> d_coeffs_out, 64 x 32 B big-endian. */
+int kzgmi_cell_batch_challenge_device(kzgmi_ctx* ctx, const void* d_commitments48, size_t m,
+                                      const void* d_commitment_indices, const void* d_cell_indices,
+                                      const void* d_cells, const void* d_proofs48, size_t n, uint8_t r_out[32]);
+int kzgmi_cell_interp_device(kzgmi_ctx* ctx, const void* d_cell_indices, const void* d_cells, size_t n,
+                             const uint8_t r32[32], void* d_coeffs_out);
+/* The whole verification, chained on the slot's stream with no host round trip.  Host buffers
+ * (staged on slot 0 like kzgmi_verify_blob_batch), device buffers, and the pipelined device form,
+ * whose verdict kzgmi_slot_wait returns.  kzgmi_last_combination works after the synchronous
+ * forms.  On a multi-device context the whole batch runs on the slot's device. */
+int kzgmi_verify_cell_batch(kzgmi_ctx* ctx, const kzgmi_cell_srs* srs, const uint8_t* commitments48, size_t m,
+                            const uint64_t* commitment_indices, const uint64_t* cell_indices, const uint8_t* cells,
+                            const uint8_t* proofs48, size_t n, const uint8_t* r32, int* ok_out);
+int kzgmi_verify_cell_batch_device(kzgmi_ctx* ctx, const kzgmi_cell_srs* srs, const void* d_commitments48, size_t m,
+                                   const void* d_commitment_indices, const void* d_cell_indices,
+                                   const void* d_cells, const void* d_proofs48, size_t n, const uint8_t* r32,
+                                   int* ok_out);
+int kzgmi_verify_cell_batch_device_async(kzgmi_ctx* ctx, const kzgmi_cell_srs* srs, int slot,
+                                         const void* d_commitments48, size_t m, const void* d_commitment_indices,
+                                         const void* d_cell_indices, const void* d_cells, const void* d_proofs48,
+                                         size_t n, const uint8_t* r32);
 
 /* Validate n device-resident G1 encodings (flags: KZGMI_FLAG_COMPRESSED,
  * KZGMI_FLAG_SUBGROUP_CHECK): 0 if all are valid, else the first error class found. */

@@ -104,7 +104,9 @@ struct Slot {
   DevBuf accq;                                   // k_accumulate's work-queue counter (large calls)
   DevBuf crowd;                                  // k_fixup's list of crowded buckets (msm.hpp k_fixup_crowded)
   DevBuf fs_leaves, fs_tmp, fs_top, pow, chal;  // Fiat-Shamir / powers-of-r randomisers
-  DevBuf blob_z, blob_y;                         // blob batches: the derived z_i, y_i (n x 32 B each)
+  DevBuf blob_z, blob_y;                         // blob batches: the derived z_i, y_i (n x 32 B each);
+                                                 // cell batches: z_k = h_k^64 and y_k = 0
+  DevBuf cell_part, cell_coef;                   // cell batches: per-coset coefficients; -c_m (64 x 8 LE words)
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -133,12 +135,14 @@ struct Slot {
     DevBuf* bufs[] = {&pts, &inf, &scal_r, &scal_s, &scal_t, &tpart, &cnt, &off, &coarse, &ent, &total, &sval, &skey,
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
-                      &acc29b, &cntb, &offb, &blob_z, &blob_y};
+                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef};
     for (DevBuf* b : bufs) f(*b);
   }
 };
 
 }  // namespace
+
+struct kzgmi_cell_srs;
 
 struct kzgmi_ctx {
   int device = 0;
@@ -224,11 +228,15 @@ struct kzgmi_ctx {
   bool blob_table_ready = false;
   // KZGMI_BLOB_HASH=lane|wave forces the blob hash's mapping (A/B, tools/bench_blobs.py); 0: blob_mapping()
   int blob_hash = 0;
+  // EIP-7594 cell front end (cell.hpp): the coset table, built at the first cell call
+  DevBuf cell_table;
+  bool cell_table_ready = false;
   DevBuf gath;                       // multi-device: partial records gathered from every device
   DevBuf mdig, mdig_all;             // multi-device Fiat-Shamir: this device's / every device's subtree roots
   std::vector<kzgmi_ctx*> peers;     // multi-device: contexts of device_ids[1..] (kzgmi_ctx_create, n_devices > 1)
   std::vector<kzgmi_srs*> srs_list;  // live SRS objects: detached (device memory freed) on destroy
   std::vector<kzgmi_ck*> ck_list;    // live commit keys: same
+  std::vector<kzgmi_cell_srs*> cell_srs_list;  // live cell SRS objects: same (their inner kzgmi_srs is in srs_list)
 };
 
 // prover commit key: rows w = 0..15 of 2^(16 w)-shifted SRS points, [row][point] Montgomery affine
@@ -250,7 +258,27 @@ struct kzgmi_srs {
   std::vector<kzgmi_srs*> peers;    // multi-device context: the same SRS on each peer device
 };
 
+// EIP-7594 cell SRS: an ordinary SRS for ([tau^0]_1, [1]_2, [tau^64]_2) and the 64 monomial points
+struct kzgmi_cell_srs {
+  kzgmi_ctx* ctx = nullptr;
+  kzgmi_srs* srs = nullptr;
+  DevBuf pts;                       // [tau^m]_1, m < 64, Montgomery affine, then their images phi([tau^m]_1) (GLV)
+  DevBuf inf;                       // the 128 infinity bytes (all zero: checked at load)
+  std::vector<kzgmi_cell_srs*> peers;  // multi-device context: the same SRS on each peer device
+};
+
 namespace {
+
+// an EIP-7594 cell batch for enqueue_batch: dC holds the m unique commitments, the device arrays
+// commitment_indices / cell_indices (uint64 x n) and cells (n x 2048 B) come with it
+struct CellJob {
+  const kzgmi_cell_srs* srs;
+  const void* cidx;
+  const void* eidx;
+  const void* cells;
+  size_t m;
+  bool derive;  // r from the transcript, on the device; else the caller's r is in the Seed
+};
 
 int set_dev(kzgmi_ctx* c) {
   HIPCHK(hipSetDevice(c->device));
@@ -348,6 +376,7 @@ int map_device_err(uint32_t e) {
     case DERR_NOT_ON_CURVE: return fail(KZGMI_ERR_NOT_ON_CURVE, "point not on curve");
     case DERR_SCALAR: return fail(KZGMI_ERR_SCALAR, "non-canonical scalar (>= r)");
     case DERR_NOT_IN_SUBGROUP: return fail(KZGMI_ERR_NOT_IN_SUBGROUP, "point not in the order-r subgroup");
+    case DERR_ARG: return fail(KZGMI_ERR_ARG, "an index read on the device is out of range (cell_index >= 128 or commitment_index >= m)");
     case DERR_SHARD: return fail(KZGMI_ERR_SHARD, "a gathered partial record is marked failed (its shard was rejected)");
     default: return fail(KZGMI_ERR_DEVICE, "unknown device error");
   }
@@ -707,12 +736,18 @@ int blob_mapping(const kzgmi_ctx* c, size_t n) {
 template <class Cv>
 int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, const void* dz, const void* dy,
                   const void* dpi, size_t n, const Seed& seed, uint64_t offset, void* d_partial_out,
-                  uint32_t flags, bool dry = false, const void* d_blobs = nullptr) {
+                  uint32_t flags, bool dry = false, const void* d_blobs = nullptr, const CellJob* cell = nullptr) {
   using XY = Xyzz<Cv>;
   using FrF = Fp<typename Cv::FrP>;
   const bool glv = c->glv_batch &&
                    (Cv::ID == 1 || (flags & (KZGMI_FLAG_SUBGROUP_CHECK | KZGMI_FLAG_TRUSTED_G1)) != 0);
-  const size_t PH = 2 * n + 1;  // GLV: phi(pts[j]) at pts[PH + j]
+  // MSM#1's tail class: -t [1]_1, or for a cell batch (BLS12-381, powers + compressed + subgroup
+  // check) the 64 terms -c_m [tau^m]_1
+  const uint32_t tail = cell ? CellLaunch::TERMS : 1;
+  // points: [pi (n) | C (n) | tail]; a cell batch keeps its m decoded unique commitments between
+  // pi and the n gathered C, so that one subgroup check covers the n + m decoded points
+  const size_t CB = n + (cell ? cell->m : 0), TB = CB + n;  // first C, first tail point
+  const size_t PH = TB + tail;  // GLV: phi(pts[j]) at pts[PH + j]
   const size_t npts = glv ? 2 * PH : PH;
   using L = Launch<Cv>;
   CHK(s.pts.ensure(npts * sizeof(Affine<Cv>)));
@@ -722,7 +757,7 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
   const bool powers = (flags & KZGMI_FLAG_POWERS) != 0;
   if (glv) {
     CHK(s.glv_s.ensure(n * 32));
-    CHK(s.glv_t.ensure(32));
+    CHK(s.glv_t.ensure((size_t)tail * 32));
     if (powers) CHK(s.glv_r.ensure(n * 32));
   }
   CHK(s.scal_r.ensure(n * (powers ? 32 : 16)));
@@ -735,6 +770,16 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
     CHK(s.blob_y.ensure(n * 32));
     CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
     CHK(s.chal.ensure(32));
+    dz = s.blob_z.p;
+    dy = s.blob_y.p;
+  }
+  if (cell) {  // cell batch: z_k = h_k^64, y_k = 0, r and the 64 coefficients are derived in front()
+    CHK(s.blob_z.ensure(n * 32));
+    CHK(s.blob_y.ensure(n * 32));
+    CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
+    CHK(s.chal.ensure(32));
+    CHK(s.cell_part.ensure(CellLaunch::part_bytes()));
+    CHK(s.cell_coef.ensure(CellLaunch::TERMS * 32));
     dz = s.blob_z.p;
     dy = s.blob_y.p;
   }
@@ -760,7 +805,10 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
     CHK(begin_job(s));
     mark(c, s, 0);
     HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, st));
-    if (flags & KZGMI_FLAG_COMPRESSED) {
+    if (cell) {  // the m unique commitments are decoded (and checked) once, then gathered
+      L::decompress_points(st, (const uint8_t*)dpi, (uint32_t)n, pts, inf, err);
+      L::decompress_points(st, (const uint8_t*)dC, (uint32_t)cell->m, pts + n, inf + n, err);
+    } else if (flags & KZGMI_FLAG_COMPRESSED) {
       L::decompress_points(st, (const uint8_t*)dpi, (uint32_t)n, pts, inf, err);
       L::decompress_points(st, (const uint8_t*)dC, (uint32_t)n, pts + n, inf + n, err);
     } else if (glv && pts29) {  // with phi(P) stored by the same pass (no k_endo_points29 over 2n points)
@@ -770,14 +818,31 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
       L::convert_points(st, (const uint8_t*)dpi, (uint32_t)n, pts, inf, err, pts29);
       L::convert_points(st, (const uint8_t*)dC, (uint32_t)n, pts + n, inf + n, err, pts29);
     }
-    if (flags & KZGMI_FLAG_SUBGROUP_CHECK) L::subgroup_check(st, pts, inf, (uint32_t)(2 * n), err);
-    // the SRS's [1]_1 as the last term of MSM#1: -t [1]_1
-    HIPCHK(hipMemcpyAsync(pts + 2 * n, pts29 ? srs->g1_29() : srs->g1.p, sizeof(Affine<Cv>), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(inf + 2 * n, srs->g1.template as<uint8_t>() + sizeof(Affine<Cv>), 1, hipMemcpyDeviceToDevice, st));
-    if (glv && pts29)  // the converts stored the 2n images: G1's alone
-      L::endo_points(st, pts + 2 * n, inf + 2 * n, 1, pts + PH + 2 * n, inf + PH + 2 * n, true);
-    else if (glv)
-      L::endo_points(st, pts, inf, (uint32_t)PH, pts + PH, inf + PH, pts29);
+    if (cell) {
+      if constexpr (Cv::ID == 0) {
+        L::subgroup_check(st, pts, inf, (uint32_t)CB, err);
+        CellLaunch::gather(st, cell->cidx, nn, (uint32_t)cell->m, pts, inf, nn, (uint32_t)CB);
+      }
+      // the cell SRS's [tau^m]_1 as the last 64 terms of MSM#1 (their images were made at SRS load)
+      const Affine<Cv>* sp = cell->srs->pts.template as<Affine<Cv>>();
+      const uint8_t* si = cell->srs->inf.template as<uint8_t>();
+      HIPCHK(hipMemcpyAsync(pts + TB, sp, tail * sizeof(Affine<Cv>), hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(inf + TB, si, tail, hipMemcpyDeviceToDevice, st));
+      if (glv) {
+        HIPCHK(hipMemcpyAsync(pts + PH + TB, sp + tail, tail * sizeof(Affine<Cv>), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(inf + PH + TB, si + tail, tail, hipMemcpyDeviceToDevice, st));
+        L::endo_points(st, pts, inf, (uint32_t)TB, pts + PH, inf + PH, false);
+      }
+    } else {
+      if (flags & KZGMI_FLAG_SUBGROUP_CHECK) L::subgroup_check(st, pts, inf, (uint32_t)(2 * n), err);
+      // the SRS's [1]_1 as the last term of MSM#1: -t [1]_1
+      HIPCHK(hipMemcpyAsync(pts + 2 * n, pts29 ? srs->g1_29() : srs->g1.p, sizeof(Affine<Cv>), hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(inf + 2 * n, srs->g1.template as<uint8_t>() + sizeof(Affine<Cv>), 1, hipMemcpyDeviceToDevice, st));
+      if (glv && pts29)  // the converts stored the 2n images: G1's alone
+        L::endo_points(st, pts + 2 * n, inf + 2 * n, 1, pts + PH + 2 * n, inf + PH + 2 * n, true);
+      else if (glv)
+        L::endo_points(st, pts, inf, (uint32_t)PH, pts + PH, inf + PH, pts29);
+    }
     mark(c, s, PH_CONVERT + 1);
     if (flags & KZGMI_FLAG_FIAT_SHAMIR) {  // r from the transcript of this (whole) batch
       const uint32_t* digests = nullptr;
@@ -790,21 +855,32 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
       BlobLaunch::eval(st, (const uint8_t*)d_blobs, bz, c->blob_table.p, (uint32_t)n, false, by, err);
       BlobLaunch::batch_challenge(st, (const uint8_t*)dC, bz, by, (const uint8_t*)dpi, (uint32_t)n, s.pow.p,
                                   s.chal.template as<uint32_t>());
+    } else if (cell && cell->derive) {  // the EIP-7594 transcript: r and its power table
+      CellLaunch::batch_challenge(st, (const uint8_t*)dC, (uint32_t)cell->m, cell->cidx, cell->eidx,
+                                  (const uint8_t*)cell->cells, (const uint8_t*)dpi, nn, s.pow.p,
+                                  s.chal.template as<uint32_t>());
     } else if (flags & KZGMI_FLAG_POWERS) {  // r supplied by the caller in place of the seed
       CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
       L::pow_table(st, seed, s.pow.p, err);
     }
+    if (cell)  // z_k = h_k^64, y_k = 0 where k_scalar_prep_pow reads them; the indices are checked here
+      CellLaunch::z(st, cell->eidx, cell->cidx, nn, (uint32_t)cell->m, c->cell_table.p, s.blob_z.template as<uint8_t>(),
+                    s.blob_y.template as<uint8_t>(), err);
     if (powers)
       L::scalar_prep_pow(st, s.pow.p, offset, (const uint8_t*)dz, (const uint8_t*)dy, (uint32_t)n,
                          s.scal_r.template as<uint32_t>(), s.scal_s.template as<uint32_t>(), s.tpart.p,
                          s.scal_t.template as<uint32_t>(), err);
-    else
+    if (cell)  // -c_m of sum_k r^k I_k, weighted by the r^k just written
+      CellLaunch::interp(st, cell->eidx, (const uint8_t*)cell->cells, s.scal_r.template as<uint32_t>(), nn,
+                         c->cell_table.p, s.cell_part.p, s.cell_coef.template as<uint32_t>(), nullptr, err);
+    if (!powers)
       L::scalar_prep(st, seed, (flags & KZGMI_FLAG_FIAT_SHAMIR) ? s.chal.template as<uint32_t>() : nullptr, offset, (const uint8_t*)dz, (const uint8_t*)dy, (uint32_t)n,
                      s.scal_r.template as<uint32_t>(), s.scal_s.template as<uint32_t>(), s.tpart.p,
                      s.scal_t.template as<uint32_t>(), err, glv ? gs : nullptr, glv ? gs + 4 * (size_t)n : nullptr);
     if (glv) {  // (s_i split by k_scalar_prep itself unless the powers form produced it)
       if (powers) L::glv_split(st, s.scal_s.template as<uint32_t>(), 8, nn, gs, gs + 4 * (size_t)n);
-      L::glv_split(st, s.scal_t.template as<uint32_t>(), 8, 1, gt, gt + 4);
+      if (cell) L::glv_split(st, s.cell_coef.template as<uint32_t>(), 8, tail, gt, gt + 4 * (size_t)tail);
+      else L::glv_split(st, s.scal_t.template as<uint32_t>(), 8, 1, gt, gt + 4);
       if (powers) L::glv_split(st, s.scal_r.template as<uint32_t>(), 8, nn, gr, gr + 4 * (size_t)n);
     }
     mark(c, s, PH_SCALARS + 1);
@@ -812,7 +888,7 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
   };
   if (!dry) CHK(front());
   TermList tl{};
-  const uint32_t ph = (uint32_t)PH;
+  const uint32_t ph = (uint32_t)PH, cb = (uint32_t)CB, tb = (uint32_t)TB;  // (cb = n, tb = 2n but for cell batches)
   // c = 16: H = 8 windows for 127-bit magnitudes, F = 16 for full scalars; c = 13: 10 and 20
   const int wb = call_wbits(c, (size_t)(powers ? 48 : 32) * n, size_t(1) << 22);
   const uint32_t H = windows_half(wb), F = windows_full(wb);
@@ -825,18 +901,18 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
     } else {
       tl.c[k++] = {nn, 0, 4, H, 0, 4, gr};                     // MSM#0: r_i pi_i = h0 pi + h1 phi(pi)
       tl.c[k++] = {nn, ph, 4, H, 0, 4, gr + 4 * (size_t)n};
-      tl.c[k++] = {nn, nn, 4, H, H, 4, gr};                    // MSM#1: r_i C_i
-      tl.c[k++] = {nn, ph + nn, 4, H, H, 4, gr + 4 * (size_t)n};
+      tl.c[k++] = {nn, cb, 4, H, H, 4, gr};                    // MSM#1: r_i C_i
+      tl.c[k++] = {nn, ph + cb, 4, H, H, 4, gr + 4 * (size_t)n};
     }
     tl.c[k++] = {nn, 0, 4, H, H, 4, gs};                       //        s_i pi_i
     tl.c[k++] = {nn, ph, 4, H, H, 4, gs + 4 * (size_t)n};
-    tl.c[k++] = {1, 2 * nn, 4, H, H, 0, gt};                   //        -t G1
-    tl.c[k++] = {1, ph + 2 * nn, 4, H, H, 0, gt + 4};
+    tl.c[k++] = {tail, tb, 4, H, H, cell ? 4u : 0u, gt};       //        -t G1 (cells: -c_m [tau^m]_1)
+    tl.c[k++] = {tail, ph + tb, 4, H, H, cell ? 4u : 0u, gt + 4 * (size_t)tail};
     tl.nclass = k;
     tl.total = 0;
     for (uint32_t j = 0; j < k; ++j) tl.total += tl.c[j].count;
     const MsmWindows mw{2, {0, H}, {H, H}};
-    CHK(run_msm_core<Cv>(c, s, tl, 2 * H, (size_t)(powers ? 6 : 4) * H * n + 2 * H + 16, mw, nullptr, nullptr,
+    CHK(run_msm_core<Cv>(c, s, tl, 2 * H, (size_t)(powers ? 6 : 4) * H * n + 2 * H * tail + 16, mw, nullptr, nullptr,
                          pts29, dry, wb));
   } else if (!powers) {  // 127-bit r_i: MSM#0 in H windows (sets 0..H-1), MSM#1 in F (sets H..H+F-1)
     tl.c[0] = {nn, 0, 4, H, 0, 4, s.scal_r.template as<uint32_t>()};          // MSM#0: r_i pi_i
@@ -846,15 +922,16 @@ int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, c
   }
   if (!glv && powers) {  // r_i = r^i, full Fr: both MSMs in F windows (sets 0..F-1, F..2F-1)
     tl.c[0] = {nn, 0, 8, F, 0, 8, s.scal_r.template as<uint32_t>()};
-    tl.c[1] = {nn, nn, 8, F, F, 8, s.scal_r.template as<uint32_t>()};
+    tl.c[1] = {nn, cb, 8, F, F, 8, s.scal_r.template as<uint32_t>()};
     tl.c[2] = {nn, 0, 8, F, F, 8, s.scal_s.template as<uint32_t>()};
     tl.c[3] = {1, 2 * nn, 8, F, F, 0, s.scal_t.template as<uint32_t>()};
+    if (cell) tl.c[3] = {tail, tb, 8, F, F, 8, s.cell_coef.template as<uint32_t>()};  // -c_m [tau^m]_1
   }
   if (!glv) {
     tl.nclass = 4;
-    tl.total = 3 * nn + 1;
+    tl.total = 3 * nn + tail;
     const MsmWindows mw = powers ? MsmWindows{2, {0, F}, {F, F}} : MsmWindows{2, {0, H}, {H, F}};
-    CHK(run_msm_core<Cv>(c, s, tl, powers ? 2 * F : H + F, (size_t)(powers ? 3 * F : 2 * H + F) * n + F + 16, mw,
+    CHK(run_msm_core<Cv>(c, s, tl, powers ? 2 * F : H + F, (size_t)(powers ? 3 * F : 2 * H + F) * n + (size_t)F * tail + 16, mw,
                          nullptr, nullptr, pts29, dry, wb));
   }
   if (dry) return 0;
@@ -1361,6 +1438,12 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
   c->lines_tmp.release();
   c->tmp.release();
   c->blob_table.release();
+  c->cell_table.release();
+  for (kzgmi_cell_srs* cs : c->cell_srs_list) {  // detach: later kzgmi_cell_srs_free() only deletes the structs
+    cs->pts.release();
+    cs->inf.release();
+    cs->ctx = nullptr;
+  }
   for (kzgmi_ck* ck : c->ck_list) {  // detach: later kzgmi_ck_free() only deletes the struct
     ck->pts.release();
     ck->inf.release();
@@ -2423,6 +2506,273 @@ int kzgmi_verify_blob_batch(kzgmi_ctx* c, const kzgmi_srs* srs, const uint8_t* b
     CHK(add_dep(s, cs));  // the batch's kernels wait for its copy only
   }
   return kzgmi_verify_blob_batch_device(c, srs, dB, dC, dpi, n, ok_out);
+}
+
+// ------------------------------------------------------------------------------ EIP-7594 cells
+}  // extern "C"
+namespace {
+constexpr size_t kCellMax = size_t(1) << 20;  // cells (and unique commitments) per call
+
+// the coset table of this context's device, once (on st, waited for)
+int ensure_cell_table(kzgmi_ctx* c, hipStream_t st) {
+  if (c->cell_table_ready) return 0;
+  CHK(c->cell_table.ensure(CellLaunch::table_bytes()));
+  CellLaunch::table(st, c->cell_table.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  c->cell_table_ready = true;
+  return 0;
+}
+
+// a live cell SRS of this context (an SRS of another kind, or of another context, is not in the list)
+bool is_cell_srs(const kzgmi_ctx* c, const kzgmi_cell_srs* cs) {
+  return cs && std::find(c->cell_srs_list.begin(), c->cell_srs_list.end(), cs) != c->cell_srs_list.end();
+}
+
+// A synchronous utility job on slot 0 whose kernels report through the slot's error word
+template <class F>
+int cell_slot0_job(kzgmi_ctx* c, F&& launch) {
+  CHK(slot0_idle(c));
+  Slot& s = c->slots[0];
+  CHK(s.flags.ensure(16));
+  CHK(ensure_cell_table(c, s.stream));
+  CHK(begin_job(s));
+  HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, s.stream));
+  CHK(launch(s, s.flags.template as<uint32_t>() + 1));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, s.stream));
+  CHK(end_job(s));
+  s.pending = true;
+  s.partial_job = true;
+  s.msm_job = false;
+  return finish_slot(c, s, nullptr);
+}
+
+Seed seed_of(const uint8_t* r32) {
+  uint8_t sb[32];
+  if (r32) return make_seed(r32, sb);
+  return Seed{};
+}
+}  // namespace
+extern "C" {
+
+void kzgmi_cell_srs_free(kzgmi_cell_srs* cs) {
+  if (!cs) return;
+  for (kzgmi_cell_srs* p : cs->peers) {
+    p->srs = nullptr;  // the inner SRS of a peer is a peer of this one's inner SRS: freed with it
+    kzgmi_cell_srs_free(p);
+  }
+  cs->peers.clear();
+  if (kzgmi_ctx* c = cs->ctx) {
+    (void)hipSetDevice(c->device);
+    auto& v = c->cell_srs_list;
+    v.erase(std::remove(v.begin(), v.end(), cs), v.end());
+    cs->pts.release();
+    cs->inf.release();
+  }
+  kzgmi_srs_free(cs->srs);
+  delete cs;
+}
+
+int kzgmi_cell_srs_load(kzgmi_ctx* c, const uint8_t* g1_monomial, const uint8_t* g2, const uint8_t* tau64_g2,
+                        kzgmi_cell_srs** out) {
+  CHK(check_ctx(c));
+  if (!g1_monomial || !g2 || !tau64_g2 || !out) return fail(KZGMI_ERR_ARG, "null cell srs argument");
+  *out = nullptr;
+  CHK(slot0_idle(c));
+  using Cv = Bls12_381;
+  using L = Launch<Cv>;
+  constexpr uint32_t T = CellLaunch::TERMS;
+  kzgmi_srs* inner = nullptr;
+  CHK(kzgmi_srs_load(c, KZGMI_BLS12_381, g1_monomial, g2, tau64_g2, &inner));  // ([tau^0]_1, [1]_2, [tau^64]_2)
+  // every device of a multi-device context gets its own copy of the 64 points
+  std::vector<kzgmi_cell_srs*> made;
+  auto undo = [&](int rc) {
+    for (kzgmi_cell_srs* m : made) {
+      m->srs = nullptr;
+      m->peers.clear();
+      kzgmi_cell_srs_free(m);
+    }
+    kzgmi_srs_free(inner);
+    return rc;
+  };
+  for (size_t d = 0; d <= c->peers.size(); ++d) {
+    kzgmi_ctx* dc = dev_ctx(c, (int)d);
+    if (int r = set_dev(dc)) return undo(r);
+    Slot& s = dc->slots[0];
+    kzgmi_cell_srs* cs = new kzgmi_cell_srs();
+    cs->ctx = dc;
+    cs->srs = d == 0 ? inner : inner->peers[d - 1];
+    dc->cell_srs_list.push_back(cs);
+    made.push_back(cs);
+    int r = 0;
+    if ((r = s.stage.ensure(T * 96)) || (r = s.flags.ensure(16)) || (r = cs->pts.ensure(2 * T * sizeof(Affine<Cv>))) ||
+        (r = cs->inf.ensure(2 * T)) || (r = begin_job(s)))
+      return undo(r);
+    hipStream_t st = s.stream;
+    Affine<Cv>* pts = cs->pts.template as<Affine<Cv>>();
+    uint8_t* inf = cs->inf.template as<uint8_t>();
+    uint8_t inf_h[T] = {};
+    bool okk = hipMemcpyAsync(s.stage.p, g1_monomial, T * 96, hipMemcpyHostToDevice, st) == hipSuccess &&
+               hipMemsetAsync(s.flags.p, 0, 16, st) == hipSuccess;
+    if (okk) {  // validated like any input point, and in G1 (GLV and the check rely on it)
+      uint32_t* err = s.flags.template as<uint32_t>() + 1;
+      L::convert_points(st, s.stage.template as<uint8_t>(), T, pts, inf, err);
+      L::subgroup_check(st, pts, inf, T, err);
+      L::endo_points(st, pts, inf, T, pts + T, inf + T, false);
+      okk = hipGetLastError() == hipSuccess &&
+            hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+            hipMemcpyAsync(inf_h, inf, T, hipMemcpyDeviceToHost, st) == hipSuccess && sync_job(s) == 0;
+    }
+    if (!okk) return undo(fail(KZGMI_ERR_DEVICE, "cell srs upload failed"));
+    int e = map_device_err((uint32_t)s.host_flags[1]);
+    for (uint32_t k = 0; !e && k < T; ++k)
+      if (inf_h[k]) e = fail(KZGMI_ERR_ARG, "cell SRS G1 element is the point at infinity");
+    if (e) return undo(e);
+  }
+  for (size_t d = 1; d < made.size(); ++d) made[0]->peers.push_back(made[d]);
+  *out = made[0];
+  return set_dev(c);
+}
+
+int kzgmi_cell_batch_challenge_device(kzgmi_ctx* c, const void* d_commitments48, size_t m,
+                                      const void* d_commitment_indices, const void* d_cell_indices,
+                                      const void* d_cells, const void* d_proofs48, size_t n, uint8_t r_out[32]) {
+  CHK(check_ctx(c));
+  if (!r_out || (m && !d_commitments48) || (n && (!d_commitment_indices || !d_cell_indices || !d_cells || !d_proofs48)))
+    return fail(KZGMI_ERR_ARG, "null argument");
+  if (n > kCellMax || m > kCellMax) return fail(KZGMI_ERR_ARG, "too many cells (max 2^20 per call)");
+  uint32_t w[8];
+  CHK(cell_slot0_job(c, [&](Slot& s, uint32_t*) -> int {
+    CHK(s.pow.ensure(FS_POW_BITS * sizeof(Fp<Bls12_381::FrP>)));
+    CHK(s.chal.ensure(32));
+    CellLaunch::batch_challenge(s.stream, (const uint8_t*)d_commitments48, (uint32_t)m, d_commitment_indices,
+                                d_cell_indices, (const uint8_t*)d_cells, (const uint8_t*)d_proofs48, (uint32_t)n,
+                                s.pow.p, s.chal.template as<uint32_t>());
+    HIPCHK(hipMemcpyAsync(w, s.chal.p, 32, hipMemcpyDeviceToHost, s.stream));
+    return 0;
+  }));
+  for (int k = 0; k < 8; ++k)
+    for (int b = 0; b < 4; ++b) r_out[4 * k + b] = (uint8_t)(w[k] >> (24 - 8 * b));
+  return 0;
+}
+
+int kzgmi_cell_interp_device(kzgmi_ctx* c, const void* d_cell_indices, const void* d_cells, size_t n,
+                             const uint8_t r32[32], void* d_coeffs_out) {
+  CHK(check_ctx(c));
+  if (!r32 || !d_coeffs_out || (n && (!d_cell_indices || !d_cells))) return fail(KZGMI_ERR_ARG, "null argument");
+  if (n > kCellMax) return fail(KZGMI_ERR_ARG, "too many cells (max 2^20 per call)");
+  using L = Launch<Bls12_381>;
+  const Seed seed = seed_of(r32);
+  return cell_slot0_job(c, [&](Slot& s, uint32_t* err) -> int {
+    const uint32_t nn = (uint32_t)n;
+    CHK(s.pow.ensure(FS_POW_BITS * sizeof(Fp<Bls12_381::FrP>)));
+    CHK(s.blob_z.ensure(n * 32));
+    CHK(s.blob_y.ensure(n * 32));
+    CHK(s.scal_r.ensure(n * 32));
+    CHK(s.scal_s.ensure(n * 32));
+    CHK(s.scal_t.ensure(32));
+    CHK(s.tpart.ensure(L::tpart_bytes(nn)));
+    CHK(s.cell_part.ensure(CellLaunch::part_bytes()));
+    CHK(s.cell_coef.ensure(CellLaunch::TERMS * 32));
+    hipStream_t st = s.stream;
+    L::pow_table(st, seed, s.pow.p, err);
+    if (n) {  // r^k through the batch path's own kernel (z_k, y_k as the batch has them)
+      CellLaunch::z(st, d_cell_indices, nullptr, nn, 0, c->cell_table.p, s.blob_z.template as<uint8_t>(),
+                    s.blob_y.template as<uint8_t>(), err);
+      L::scalar_prep_pow(st, s.pow.p, 0, s.blob_z.template as<uint8_t>(), s.blob_y.template as<uint8_t>(), nn,
+                         s.scal_r.template as<uint32_t>(), s.scal_s.template as<uint32_t>(), s.tpart.p,
+                         s.scal_t.template as<uint32_t>(), err);
+    }
+    CellLaunch::interp(st, d_cell_indices, (const uint8_t*)d_cells, s.scal_r.template as<uint32_t>(), nn,
+                       c->cell_table.p, s.cell_part.p, s.cell_coef.template as<uint32_t>(), (uint8_t*)d_coeffs_out, err);
+    return 0;
+  });
+}
+
+int kzgmi_verify_cell_batch_device_async(kzgmi_ctx* c, const kzgmi_cell_srs* csrs, int slot,
+                                         const void* d_commitments48, size_t m, const void* d_commitment_indices,
+                                         const void* d_cell_indices, const void* d_cells, const void* d_proofs48,
+                                         size_t n, const uint8_t* r32) {
+  if (!c) return fail(KZGMI_ERR_ARG, "null context");
+  if (!is_cell_srs(c, csrs)) return fail(KZGMI_ERR_ARG, "not a cell srs of this context (kzgmi_cell_srs_load)");
+  {
+    kzgmi_ctx* c0 = c;
+    const int slot0 = slot;
+    KZ_ROUTE(c, nullptr, slot);
+    if (c != c0) {  // a peer device of a multi-device context: its copy of the SRS
+      const int D = 1 + (int)c0->peers.size();
+      if (csrs->peers.size() != c0->peers.size()) return fail(KZGMI_ERR_ARG, "cell srs does not belong to this context");
+      csrs = csrs->peers[slot0 % D - 1];
+    }
+    CHK(check_ctx(c, slot));
+    if (n && (!d_commitments48 || !d_commitment_indices || !d_cell_indices || !d_cells || !d_proofs48))
+      return fail(KZGMI_ERR_ARG, "null input");
+    if (n > kCellMax || m > kCellMax) return fail(KZGMI_ERR_ARG, "too many cells (max 2^20 per call)");
+    if (n && !m) return fail(KZGMI_ERR_ARG, "cells without commitments");
+    Slot& s = c->slots[slot];
+    if (s.pending) return fail(KZGMI_ERR_ARG, "slot busy: call kzgmi_slot_wait first");
+    if (n == 0) {  // accepts
+      CHK(sync_slot(s));  // host_flags may still be the target of a copy
+      s.host_flags[0] = 1;
+      s.host_flags[1] = 0;
+      s.pending = true;
+      s.partial_job = false;
+      s.partial_of = 0;
+      s.msm_job = false;
+      return 0;
+    }
+    Roctx rx("kzgmi_verify_cell_batch_device_async");
+    CHK(ensure_cell_table(c, s.stream));
+    const CellJob job{csrs, d_commitment_indices, d_cell_indices, d_cells, m, r32 == nullptr};
+    return enqueue_batch<Bls12_381>(c, s, csrs->srs, d_commitments48, nullptr, nullptr, d_proofs48, n, seed_of(r32), 0,
+                                    nullptr, kBlobFlags, /*dry=*/false, nullptr, &job);
+  }
+}
+
+int kzgmi_verify_cell_batch_device(kzgmi_ctx* c, const kzgmi_cell_srs* csrs, const void* d_commitments48, size_t m,
+                                   const void* d_commitment_indices, const void* d_cell_indices, const void* d_cells,
+                                   const void* d_proofs48, size_t n, const uint8_t* r32, int* ok_out) {
+  if (!c) return fail(KZGMI_ERR_ARG, "null context");
+  if (!ok_out) return fail(KZGMI_ERR_ARG, "null ok_out");
+  c->sync_call = true;
+  const int rc = kzgmi_verify_cell_batch_device_async(c, csrs, 0, d_commitments48, m, d_commitment_indices,
+                                                      d_cell_indices, d_cells, d_proofs48, n, r32);
+  c->sync_call = false;
+  CHK(rc);
+  return kzgmi_slot_wait(c, 0, ok_out);
+}
+
+int kzgmi_verify_cell_batch(kzgmi_ctx* c, const kzgmi_cell_srs* csrs, const uint8_t* commitments48, size_t m,
+                            const uint64_t* commitment_indices, const uint64_t* cell_indices, const uint8_t* cells,
+                            const uint8_t* proofs48, size_t n, const uint8_t* r32, int* ok_out) {
+  CHK(check_ctx(c));
+  if (!ok_out) return fail(KZGMI_ERR_ARG, "null argument");
+  if (!is_cell_srs(c, csrs)) return fail(KZGMI_ERR_ARG, "not a cell srs of this context (kzgmi_cell_srs_load)");
+  if (n && (!commitments48 || !commitment_indices || !cell_indices || !cells || !proofs48))
+    return fail(KZGMI_ERR_ARG, "null input");
+  if (n > kCellMax || m > kCellMax) return fail(KZGMI_ERR_ARG, "too many cells (max 2^20 per call)");
+  CHK(slot0_idle(c));
+  Slot& s = c->slots[0];
+  uint8_t *dC = nullptr, *dci = nullptr, *dei = nullptr, *dcl = nullptr, *dpi = nullptr;
+  if (n) {  // the five arrays into the slot's stage buffer (16-byte aligned) on the FIFO copy stream
+    const size_t ib = (8 * n + 15) / 16 * 16;
+    CHK(s.stage.ensure(48 * m + 2 * ib + n * (CellLaunch::BYTES + 48) + 16));
+    dC = s.stage.template as<uint8_t>();
+    dci = dC + 48 * m;
+    dei = dci + ib;
+    dcl = dei + ib;
+    dpi = dcl + n * CellLaunch::BYTES;
+    hipStream_t cs = c->h2d_stream;
+    if (s.done_rec) HIPCHK(hipStreamWaitEvent(cs, s.done_ev, 0));  // the stage buffer is free
+    if (m) CHK(h2d(s, cs, dC, commitments48, 48 * m));
+    CHK(h2d(s, cs, dci, commitment_indices, 8 * n));
+    CHK(h2d(s, cs, dei, cell_indices, 8 * n));
+    CHK(h2d(s, cs, dcl, cells, n * CellLaunch::BYTES));
+    CHK(h2d(s, cs, dpi, proofs48, 48 * n));
+    CHK(add_dep(s, cs));  // the batch's kernels wait for its copy only
+  }
+  return kzgmi_verify_cell_batch_device(c, csrs, dC, m, dci, dei, dcl, dpi, n, r32, ok_out);
 }
 
 int kzgmi_g1_compress_device(kzgmi_ctx* c, kzgmi_curve curve, const void* d_points, size_t n, void* d_out) {

@@ -10,8 +10,9 @@ namespace kzgmi {
 
 // device-side error codes (atomicMax into the context's error word; host maps to KZGMI_ERR_*)
 // DERR_SHARD: a gathered partial record was marked failed without a code of its own (k_sum_partials)
+// DERR_ARG: an index read on the device is out of range (cell.hpp: cell / commitment indices)
 enum : uint32_t { DERR_NONE = 0, DERR_ENCODING = 1, DERR_NOT_ON_CURVE = 2, DERR_SCALAR = 3, DERR_NOT_IN_SUBGROUP = 4,
-                  DERR_SHARD = 5 };
+                  DERR_SHARD = 5, DERR_ARG = 6 };
 
 KZ_DEV void raise_err(uint32_t* err, uint32_t code) { atomicMax(err, code); }
 

@@ -129,6 +129,30 @@ struct BlobLaunch {
                               const uint8_t* proofs, uint32_t n, void* pow, uint32_t* chal_out);
 };
 
+// ---- EIP-7594 cell front end (cell.hpp, launch_cell.hip): BLS12-381 only, 64-element cells on 128 cosets
+struct CellLaunch {
+  static constexpr size_t BYTES = 64 * 32;          // one cell
+  static constexpr uint32_t TERMS = 64;             // [tau^m]_1, m < 64: MSM#1's tail class
+  static size_t table_bytes();                      // the coset table
+  static size_t part_bytes();                       // per-coset coefficients: 128 x 64 Fr
+  static void table(hipStream_t st, void* table);
+  // z_k = h_k^64 -> zs, y_k = 0 -> ys (n x 32 B each); indices out of range raise DERR_ARG
+  // (commitment_indices may be null: not checked)
+  static void z(hipStream_t st, const void* cell_indices, const void* commitment_indices, uint32_t n, uint32_t m,
+                const void* table, uint8_t* zs, uint8_t* ys, uint32_t* err);
+  // pts[dst + k] = pts[src + commitment_indices[k]] (with the infinity flags)
+  static void gather(hipStream_t st, const void* commitment_indices, uint32_t n, uint32_t m, Affine<Bls12_381>* pts,
+                     uint8_t* inf, uint32_t src, uint32_t dst);
+  // c_m of sum_k r^k I_k (rk: r^k as 8 LE words each): -c_m as LE words -> neg_le (64 x 8 words),
+  // c_m as 32 B big-endian -> coeffs_be (may be null); every cell element range-checked
+  static void interp(hipStream_t st, const void* cell_indices, const uint8_t* cells, const uint32_t* rk, uint32_t n,
+                     const void* table, void* part, uint32_t* neg_le, uint8_t* coeffs_be, uint32_t* err);
+  // r of the batch -> chal_out (8 big-endian words) and the power table of scalar_prep_pow
+  static void batch_challenge(hipStream_t st, const uint8_t* commitments, uint32_t m, const void* commitment_indices,
+                              const void* cell_indices, const uint8_t* cells, const uint8_t* proofs, uint32_t n,
+                              void* pow, uint32_t* chal_out);
+};
+
 inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace kzgmi

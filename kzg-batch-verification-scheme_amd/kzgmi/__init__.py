@@ -102,6 +102,13 @@ def lib():
         "kzgmi_verify_blob_batch": ([vp, vp, vp, vp, vp, sz, ip], c.c_int),
         "kzgmi_verify_blob_batch_device": ([vp, vp, vp, vp, vp, sz, ip], c.c_int),
         "kzgmi_verify_blob_batch_device_async": ([vp, vp, c.c_int, vp, vp, vp, sz], c.c_int),
+        "kzgmi_cell_srs_load": ([vp, u8p, u8p, u8p, c.POINTER(vp)], c.c_int),
+        "kzgmi_cell_srs_free": ([vp], None),
+        "kzgmi_cell_batch_challenge_device": ([vp, vp, sz, vp, vp, vp, vp, sz, u8p], c.c_int),
+        "kzgmi_cell_interp_device": ([vp, vp, vp, sz, u8p, vp], c.c_int),
+        "kzgmi_verify_cell_batch": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, u8p, ip], c.c_int),
+        "kzgmi_verify_cell_batch_device": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, u8p, ip], c.c_int),
+        "kzgmi_verify_cell_batch_device_async": ([vp, vp, c.c_int, vp, sz, vp, vp, vp, vp, sz, u8p], c.c_int),
         "kzgmi_slot_wait": ([vp, c.c_int, ip], c.c_int),
         "kzgmi_last_combination": ([vp, u8p, u8p], c.c_int),
         "kzgmi_msm_g1": ([vp, c.c_int, vp, vp, sz, u8p], c.c_int),
@@ -162,6 +169,8 @@ def exported_symbols():
         "kzgmi_host_alloc", "kzgmi_host_free", "kzgmi_host_register", "kzgmi_host_unregister",
         "kzgmi_blob_challenges_device", "kzgmi_blob_eval_device", "kzgmi_blob_batch_challenge_device",
         "kzgmi_verify_blob_batch", "kzgmi_verify_blob_batch_device", "kzgmi_verify_blob_batch_device_async",
+        "kzgmi_cell_srs_load", "kzgmi_cell_srs_free", "kzgmi_cell_batch_challenge_device", "kzgmi_cell_interp_device",
+        "kzgmi_verify_cell_batch", "kzgmi_verify_cell_batch_device", "kzgmi_verify_cell_batch_device_async",
     ]
 
 
@@ -173,6 +182,8 @@ FLAG_TRUSTED_G1 = 16
 ERR_NOT_IN_SUBGROUP = -7
 FS_CHUNK = 4096
 BLOB_BYTES = 4096 * 32  # an EIP-4844 blob: 4096 big-endian canonical Fr elements
+CELL_BYTES = 64 * 32    # an EIP-7594 cell: 64 big-endian canonical Fr elements
+CELLS_PER_EXT_BLOB = 128
 
 
 def _flags(compressed: bool = False, subgroup_check: bool = False, fiat_shamir: bool = False,
@@ -327,6 +338,37 @@ class Srs:
                 self.handle = None
         except Exception:
             pass
+
+
+@dataclass
+class CellSrs:
+    """EIP-7594 cell SRS: [tau^m]_1 for m < 64, [1]_2, [tau^64]_2 (kzgmi_cell_srs_load)."""
+    ctx: "Context"
+    handle: ctypes.c_void_p
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().kzgmi_cell_srs_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def _u64_bytes(xs) -> bytes:
+    """A sequence of indices as uint64 little-endian bytes (bytes-like input is passed through)."""
+    if isinstance(xs, (bytes, bytearray, memoryview)):
+        return bytes(xs)
+    import struct
+    xs = [int(x) for x in xs]
+    return struct.pack("<%dQ" % len(xs), *xs)
+
+
+def _r32(r):
+    """The optional caller-supplied batch challenge as a 32-byte big-endian buffer (None: derive)."""
+    if r is None:
+        return None
+    return int(r).to_bytes(32, "big") if isinstance(r, int) else bytes(r)
 
 
 class CommitKey:
@@ -671,6 +713,83 @@ class Context:
         self._order(slot)
         _check(lib().kzgmi_verify_blob_batch_device_async(self.handle, srs.handle, int(slot), *ptrs, int(n)))
 
+    # ------------------------------------------------------------------ EIP-7594 cells
+    def load_cell_srs(self, g1_monomial: bytes, g2: bytes, tau64_g2: bytes) -> CellSrs:
+        """The cell SRS: g1_monomial = [tau^m]_1 for m < 64 (64 x 96 B), [1]_2, [tau^64]_2."""
+        if len(g1_monomial) != 64 * 96:
+            raise ValueError("g1_monomial must hold 64 uncompressed G1 points (6144 bytes)")
+        h = ctypes.c_void_p()
+        _check(lib().kzgmi_cell_srs_load(self.handle, bytes(g1_monomial), bytes(g2), bytes(tau64_g2), ctypes.byref(h)))
+        return CellSrs(self, h)
+
+    @staticmethod
+    def _cell_srs_handle(srs):
+        if not isinstance(srs, CellSrs):
+            raise KzgmiError(-1, "not a cell SRS (Context.load_cell_srs)")
+        return srs.handle
+
+    def cell_batch_challenge(self, commitments, commitment_indices, cell_indices, cells, proofs, m: int, n: int) -> int:
+        """r of verify_cell_kzg_proof_batch's transcript for device-resident arrays: m unique 48-byte
+        commitments, n uint64 commitment indices and cell indices, n cells (2048 B), n 48-byte proofs."""
+        out = ctypes.create_string_buffer(32)
+        ptrs = (_dptr(commitments, 48 * m), int(m), _dptr(commitment_indices, 8 * n), _dptr(cell_indices, 8 * n),
+                _dptr(cells, CELL_BYTES * n), _dptr(proofs, 48 * n))
+        self._order(0)
+        _check(lib().kzgmi_cell_batch_challenge_device(self.handle, *ptrs, int(n), out))
+        return int.from_bytes(out.raw, "big")
+
+    def cell_interp(self, cell_indices, cells, n: int, r, out=None):
+        """The 64 coefficients c_m of sum_k r^k I_k (I_k: cell k's interpolation polynomial on its
+        coset) for device-resident uint64 cell indices and cells: a device tensor of 64 x 32 B."""
+        import torch
+        if out is None:
+            out = torch.empty(32 * 64, dtype=torch.uint8, device=cells.device)
+        pi, pc, po = _dptr(cell_indices, 8 * n), _dptr(cells, CELL_BYTES * n), _dptr(out, 32 * 64)
+        self._order(0)
+        _check(lib().kzgmi_cell_interp_device(self.handle, pi, pc, int(n), _r32(r), po))
+        return out
+
+    def verify_cell_batch(self, srs: CellSrs, commitments, commitment_indices, cell_indices, cells, proofs,
+                          m: Optional[int] = None, n: Optional[int] = None, r=None) -> bool:
+        """verify_cell_kzg_proof_batch in its deduplicated form: m unique compressed commitments, n
+        uint64 commitment indices and cell indices, n cells and n compressed proofs, as host buffers
+        or device tensors (indices on the host may be Python sequences).  r: the batch challenge
+        if the caller hashed the transcript itself; None derives it on the GPU."""
+        ok = ctypes.c_int(-1)
+        h = self._cell_srs_handle(srs)
+        if _is_device_tensor(cells):
+            if n is None:
+                n = proofs.numel() // 48
+            if m is None:
+                m = commitments.numel() // 48
+            ptrs = (_dptr(commitments, 48 * m), int(m), _dptr(commitment_indices, 8 * n), _dptr(cell_indices, 8 * n),
+                    _dptr(cells, CELL_BYTES * n), _dptr(proofs, 48 * n))
+            self._order(0)
+            _check(lib().kzgmi_verify_cell_batch_device(self.handle, h, *ptrs, int(n), _r32(r), ctypes.byref(ok)))
+        else:
+            ci, ce = _u64_bytes(commitment_indices), _u64_bytes(cell_indices)
+            (pc, lc, kc), (pi, li, ki), (pe, le, ke), (pl, ll, kl), (pp, lp, kp) = (
+                _host_ptr(v) for v in (commitments, ci, ce, cells, proofs))
+            if n is None:
+                n = lp // 48
+            if m is None:
+                m = lc // 48
+            if lc < 48 * m or li < 8 * n or le < 8 * n or ll < CELL_BYTES * n or lp < 48 * n:
+                raise ValueError("input buffers shorter than n cells")
+            _check(lib().kzgmi_verify_cell_batch(self.handle, h, pc, int(m), pi, pe, pl, pp, int(n), _r32(r),
+                                                 ctypes.byref(ok)))
+            del kc, ki, ke, kl, kp
+        return bool(ok.value)
+
+    def verify_cell_batch_async(self, srs: CellSrs, slot: int, commitments, commitment_indices, cell_indices, cells,
+                                proofs, m: int, n: int, r=None):
+        """Enqueue verify_cell_batch of device tensors on `slot`; wait(slot) returns the verdict."""
+        h = self._cell_srs_handle(srs)
+        ptrs = (_dptr(commitments, 48 * m), int(m), _dptr(commitment_indices, 8 * n), _dptr(cell_indices, 8 * n),
+                _dptr(cells, CELL_BYTES * n), _dptr(proofs, 48 * n))
+        self._order(slot)
+        _check(lib().kzgmi_verify_cell_batch_device_async(self.handle, h, int(slot), *ptrs, int(n), _r32(r)))
+
     def wait(self, slot: int) -> bool:
         ok = ctypes.c_int(-1)
         try:
@@ -899,6 +1018,27 @@ def batch_verify(commitments, zs, ys, proofs, srs: Srs, seed: Optional[bytes] = 
 def verify_blob_batch(blobs, commitments, proofs, srs: Srs, n: Optional[int] = None) -> bool:
     """EIP-4844 verify_blob_kzg_proof_batch(blobs, commitments, proofs) on the GPU (BLS12-381)."""
     return srs.ctx.verify_blob_batch(srs, blobs, commitments, proofs, n=n)
+
+
+def verify_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs: CellSrs, r=None) -> bool:
+    """EIP-7594 verify_cell_kzg_proof_batch(commitments_bytes, cell_indices, cells, proofs_bytes) on
+    the GPU (BLS12-381): lists of 48-byte commitments (one per cell, repeats allowed), cell
+    indices, 2048-byte cells and 48-byte proofs.  Commitments are deduplicated here, in order of
+    first appearance."""
+    n = len(cells)
+    if not (len(commitments_bytes) == len(cell_indices) == len(proofs_bytes) == n):
+        raise ValueError("commitments, cell indices, cells and proofs must have the same length")
+    index, unique, cidx = {}, [], []
+    for cm in commitments_bytes:
+        cm = bytes(cm)
+        if cm not in index:
+            index[cm] = len(unique)
+            unique.append(cm)
+        cidx.append(index[cm])
+    if not isinstance(srs, CellSrs):
+        raise KzgmiError(-1, "not a cell SRS (Context.load_cell_srs)")
+    return srs.ctx.verify_cell_batch(srs, b"".join(unique), cidx, list(cell_indices), b"".join(bytes(x) for x in cells),
+                                     b"".join(bytes(p) for p in proofs_bytes), m=len(unique), n=n, r=r)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:

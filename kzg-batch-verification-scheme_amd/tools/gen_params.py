@@ -207,6 +207,17 @@ def blob_root(r):
     return w
 
 
+CELL_DOMAIN = 8192  # FIELD_ELEMENTS_PER_EXT_BLOB of EIP-7594: the cells' cosets live in the extended domain
+
+
+def cell_root(r):
+    """The primitive 8192nd root of unity 7^((r-1)/8192) mod r (EIP-7594); its square is blob_root(r)."""
+    assert (r - 1) % CELL_DOMAIN == 0
+    w = pow(7, (r - 1) // CELL_DOMAIN, r)
+    assert pow(w, CELL_DOMAIN // 2, r) == r - 1 and w * w % r == blob_root(r)
+    return w
+
+
 def main():
     out = ["// GENERATED by tools/gen_params.py -- do not edit.",
            "// 32-bit little-endian limbs; *_M = Montgomery form (R = 2^(32*N)).",
@@ -249,6 +260,8 @@ def main():
         if name == "Bls12_381":  # EIP-4844 blob domain (blob.hpp): omega = 7^((r-1)/4096), order 4096
             w = blob_root(r)
             out.append("  static constexpr uint32_t ROOT4096_M[N] = %s;  // 7^((r-1)/4096), Montgomery" % arr(w * Rr % r, 8))
+            w2 = cell_root(r)  # EIP-7594 cell cosets (cell.hpp): order 8192
+            out.append("  static constexpr uint32_t ROOT8192_M[N] = %s;  // 7^((r-1)/8192), Montgomery" % arr(w2 * Rr % r, 8))
         out.append("};")
         xi = c["xi"]
         if c["twist"] == "M":
