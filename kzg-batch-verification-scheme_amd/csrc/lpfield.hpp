@@ -21,7 +21,8 @@
 // canonicalise in uniform scalar code (lp_canon: quotient estimate in double precision from the
 // top limbs, exact multi-limb correction).
 // Reference: none (LICENSE only); checked through every MSM / batch parity test (the window
-// combination of every MSM runs here) and kzgmi_selftest_lp.
+// combination of every MSM runs here) and op by op, at the edges of these bounds, against a
+// big-integer reference by tests/test_gpu_field.py (lp.* ops of tests/native/field_probe.hip).
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -84,7 +85,7 @@ KZ_DEV LpCtx<Cv> lp_ctx() {
   return c;
 }
 
-// one carry pass: limbs back into [-2, 2^29 + 2) for inputs |v| < 2^30.6
+// one carry pass: limbs back into [-4, 2^29 + 3) for inputs |v| < 2^30.6 (the carry v >> 29 lies in [-4, 3])
 template <class Cv>
 KZ_DEV int32_t lp_norm(const LpCtx<Cv>& c, int32_t v) {
   const int32_t carry = (v >> 29) & c.cmask;

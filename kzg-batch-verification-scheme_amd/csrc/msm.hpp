@@ -824,7 +824,9 @@ KZ_DEV Xyzz<Cv> x29_to32(const X29<Q>& a) {
   return {fp_from29<Q, P>(a.x), fp_from29<Q, P>(a.y), fp_from29<Q, P>(a.zz), fp_from29<Q, P>(a.zzz)};
 }
 // 2a (dbl-2008-s-1, a = 0).  Inputs within the record bounds; outputs x < 5.1p, y, zz, zzz <
-// 1.01p.  BLS12-381 G1 has no 2-torsion (#E(Fp) is odd), so only O doubles to O.
+// 1.01p on BLS12-381; on BN254 (R29 / p ~ 169) x < 5.2p, y < 1.5p, zz, zzz < 1.1p (the same steps
+// of tools/gen_params29.py check_bounds, asserted per curve by tests/test_gpu_field.py).
+// BLS12-381 G1 has no 2-torsion (#E(Fp) is odd), so only O doubles to O.
 template <class Q>
 KZ_DEV X29<Q> x29_dbl(const X29<Q>& a) {
   using G = F29<Q>;
@@ -845,7 +847,8 @@ KZ_DEV X29<Q> x29_dbl(const X29<Q>& a) {
 }
 
 // a + b (add-2008-s, 12M + 2S with the Y3 pair sharing one reduction).  Inputs within the record
-// bounds (x < 10p, y < 16p, zz, zzz < 2p); outputs x < 9.1p, y, zz, zzz < 1.01p -- inside them.
+// bounds (x < 10p, y < 16p, zz, zzz < 2p); outputs x < 9.1p, y, zz, zzz < 1.01p (BN254: y < 1.4p)
+// -- inside them.
 template <class Cv, class Q>
 KZ_DEV X29<Q> x29_add(const X29<Q>& a, const X29<Q>& b) {
   using G = F29<Q>;
