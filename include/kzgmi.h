@@ -64,7 +64,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * marked record), kzgmi_stream_wait orders the slot's NEXT job, multi-device contexts pipeline
  * whole batches per device through the async entry points (kzgmi_slot_device).  6: the EIP-4844
  * blob entry points kzgmi_blob_*_device and kzgmi_verify_blob_batch* were added; still 6 (additive):
- * the EIP-7594 cell entry points kzgmi_cell_* and kzgmi_verify_cell_batch*.  A caller built
+ * the EIP-7594 cell entry points kzgmi_cell_* and kzgmi_verify_cell_batch*, and the cell extension
+ * and recovery entry points kzgmi_compute_cells* and kzgmi_recover_cells*.  A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
 
@@ -345,6 +346,37 @@ int kzgmi_verify_cell_batch_device_async(kzgmi_ctx* ctx, const kzgmi_cell_srs* s
                                          const void* d_commitments48, size_t m, const void* d_commitment_indices,
                                          const void* d_cell_indices, const void* d_cells, const void* d_proofs48,
                                          size_t n, const uint8_t* r32);
+
+/* ---- EIP-7594 cell extension and recovery (compute_cells, and the cells of
+ * recover_cells_and_kzg_proofs; cell PROOFS are not generated) -- BLS12-381 only, with the cell
+ * conventions above.  A blob is 4096 x 32 B big-endian canonical Fr, blob[k] = p(dom[k]) with
+ * dom[k] = (w^2)^rev12(k) and deg p < 4096; its 128 cells are 8192 x 32 B = 256 KiB, cell i at byte
+ * 2048 i.  An input element >= r: KZGMI_ERR_SCALAR.
+ * compute_cells: blobs (nb x 128 KiB) -> cells_out (nb x 256 KiB).  Cells 0..63 are the blob's bytes
+ * (rev13(k) = 2 rev12(k) for k < 4096), cells 64..127 are p on w * dom[k], in the same order.
+ * recover_cells: k distinct cell indices (uint64, any order, 64 <= k <= 128) SHARED by all nb blobs
+ * of the call -- the column shape: the same columns of every blob of a block -- and nb x k cells
+ * (cells of blob b at byte 2048 k b, in the order of the indices) -> cells_out, all 128 cells of
+ * every blob.  The input of one blob is CONSISTENT if some polynomial of degree < 4096 takes all
+ * 64 k given values; it is then unique and the output is its 128 cells, bit-exact.  With k = 64
+ * every input is consistent.  If any blob's input is inconsistent the call fails with
+ * KZGMI_ERR_ARG and the outputs are unspecified.  k < 64 or k > 128 (checked on the host), a cell
+ * index >= 128 or a duplicate index (found on the device): KZGMI_ERR_ARG.
+ * nb == 0 succeeds and writes nothing; nb > 4096: KZGMI_ERR_ARG.  Device arrays are 16-byte aligned;
+ * outputs must not overlap inputs.  The host-buffer forms stage through slot 0 (like
+ * kzgmi_verify_blob_batch) and copy the result back; the synchronous device forms run on slot 0;
+ * the async forms run on any slot and complete with kzgmi_slot_wait (ok_out = 1), which reports
+ * the device-side errors above.  On a multi-device context the job runs on the slot's device.
+ * Scratch lives in the slot's workspace (grown on first use, counted by kzgmi_alloc_count). */
+int kzgmi_compute_cells(kzgmi_ctx* ctx, const uint8_t* blobs, size_t nb, uint8_t* cells_out);
+int kzgmi_compute_cells_device(kzgmi_ctx* ctx, const void* d_blobs, size_t nb, void* d_cells_out);
+int kzgmi_compute_cells_device_async(kzgmi_ctx* ctx, int slot, const void* d_blobs, size_t nb, void* d_cells_out);
+int kzgmi_recover_cells(kzgmi_ctx* ctx, const uint64_t* cell_indices, size_t k, const uint8_t* cells, size_t nb,
+                        uint8_t* cells_out);
+int kzgmi_recover_cells_device(kzgmi_ctx* ctx, const void* d_cell_indices, size_t k, const void* d_cells, size_t nb,
+                               void* d_cells_out);
+int kzgmi_recover_cells_device_async(kzgmi_ctx* ctx, int slot, const void* d_cell_indices, size_t k,
+                                     const void* d_cells, size_t nb, void* d_cells_out);
 
 /* Validate n device-resident G1 encodings (flags: KZGMI_FLAG_COMPRESSED,
  * KZGMI_FLAG_SUBGROUP_CHECK): 0 if all are valid, else the first error class found. */

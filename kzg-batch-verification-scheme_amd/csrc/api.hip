@@ -107,6 +107,7 @@ struct Slot {
   DevBuf blob_z, blob_y;                         // blob batches: the derived z_i, y_i (n x 32 B each);
                                                  // cell batches: z_k = h_k^64 and y_k = 0
   DevBuf cell_part, cell_coef;                   // cell batches: per-coset coefficients; -c_m (64 x 8 LE words)
+  DevBuf rec_z;                                  // recover_cells: the call's vanishing-polynomial table (recover.hpp)
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -135,7 +136,7 @@ struct Slot {
     DevBuf* bufs[] = {&pts, &inf, &scal_r, &scal_s, &scal_t, &tpart, &cnt, &off, &coarse, &ent, &total, &sval, &skey,
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
-                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef};
+                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z};
     for (DevBuf* b : bufs) f(*b);
   }
 };
@@ -231,6 +232,9 @@ struct kzgmi_ctx {
   // EIP-7594 cell front end (cell.hpp): the coset table, built at the first cell call
   DevBuf cell_table;
   bool cell_table_ready = false;
+  // EIP-7594 cell extension and recovery (recover.hpp): twiddles and scale factors, built at the first such call
+  DevBuf ntt_table;
+  bool ntt_table_ready = false;
   DevBuf gath;                       // multi-device: partial records gathered from every device
   DevBuf mdig, mdig_all;             // multi-device Fiat-Shamir: this device's / every device's subtree roots
   std::vector<kzgmi_ctx*> peers;     // multi-device: contexts of device_ids[1..] (kzgmi_ctx_create, n_devices > 1)
@@ -376,7 +380,7 @@ int map_device_err(uint32_t e) {
     case DERR_NOT_ON_CURVE: return fail(KZGMI_ERR_NOT_ON_CURVE, "point not on curve");
     case DERR_SCALAR: return fail(KZGMI_ERR_SCALAR, "non-canonical scalar (>= r)");
     case DERR_NOT_IN_SUBGROUP: return fail(KZGMI_ERR_NOT_IN_SUBGROUP, "point not in the order-r subgroup");
-    case DERR_ARG: return fail(KZGMI_ERR_ARG, "an index read on the device is out of range (cell_index >= 128 or commitment_index >= m)");
+    case DERR_ARG: return fail(KZGMI_ERR_ARG, "an index read on the device is out of range (cell_index >= 128 or commitment_index >= m) or repeated, or the cells given to recover_cells are inconsistent");
     case DERR_SHARD: return fail(KZGMI_ERR_SHARD, "a gathered partial record is marked failed (its shard was rejected)");
     default: return fail(KZGMI_ERR_DEVICE, "unknown device error");
   }
@@ -1439,6 +1443,7 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
   c->tmp.release();
   c->blob_table.release();
   c->cell_table.release();
+  c->ntt_table.release();
   for (kzgmi_cell_srs* cs : c->cell_srs_list) {  // detach: later kzgmi_cell_srs_free() only deletes the structs
     cs->pts.release();
     cs->inf.release();
@@ -2773,6 +2778,148 @@ int kzgmi_verify_cell_batch(kzgmi_ctx* c, const kzgmi_cell_srs* csrs, const uint
     CHK(add_dep(s, cs));  // the batch's kernels wait for its copy only
   }
   return kzgmi_verify_cell_batch_device(c, csrs, dC, m, dci, dei, dcl, dpi, n, r32, ok_out);
+}
+
+// ------------------------------------------------------------------------------ EIP-7594 cell extension / recovery
+}  // extern "C"
+namespace {
+constexpr size_t kRecoverMaxBlobs = 4096;  // blobs per call: 256 KiB of output each
+
+// the transform table of this context's device, once (on st, waited for)
+int ensure_ntt_table(kzgmi_ctx* c, hipStream_t st) {
+  if (c->ntt_table_ready) return 0;
+  CHK(c->ntt_table.ensure(RecoverLaunch::table_bytes()));
+  RecoverLaunch::table(st, c->ntt_table.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  c->ntt_table_ready = true;
+  return 0;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+// The argument checks every form shares; d_idx == nullptr: compute_cells (in: nb blobs), else
+// recover_cells (in: nb x k cells)
+int check_cells_args(const void* d_idx, size_t k, const void* d_in, size_t nb, const void* d_out, bool device) {
+  if (d_idx && (k < RecoverLaunch::MIN_CELLS || k > RecoverLaunch::MAX_CELLS))
+    return fail(KZGMI_ERR_ARG, "recover_cells takes 64 to 128 cells per blob");
+  if (nb > kRecoverMaxBlobs) return fail(KZGMI_ERR_ARG, "too many blobs (max 4096 per call)");
+  if (nb && (!d_in || !d_out)) return fail(KZGMI_ERR_ARG, "null argument");
+  if (!device || nb == 0) return 0;
+  if (((uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)d_idx) & 15) return fail(KZGMI_ERR_ARG, "device arrays must be 16-byte aligned");
+  const size_t in_bytes = nb * (d_idx ? k * CellLaunch::BYTES : BlobLaunch::BYTES);
+  if (ranges_overlap(d_in, in_bytes, d_out, nb * RecoverLaunch::OUT_BYTES) ||
+      (d_idx && ranges_overlap(d_idx, 8 * k, d_out, nb * RecoverLaunch::OUT_BYTES)))
+    return fail(KZGMI_ERR_ARG, "the output overlaps an input");
+  return 0;
+}
+
+// One extension / recovery job on slot s (any slot): completes with kzgmi_slot_wait like a partial
+// job, its kernels reporting through the slot's error word
+int enqueue_cells_job(kzgmi_ctx* c, Slot& s, const void* d_idx, size_t k, const void* d_in, size_t nb, void* d_out) {
+  if (s.pending) return fail(KZGMI_ERR_ARG, "slot busy: call kzgmi_slot_wait first");
+  if (nb == 0) {  // succeeds, writes nothing
+    CHK(sync_slot(s));  // host_flags may still be the target of a copy
+    s.host_flags[0] = 1;
+    s.host_flags[1] = 0;
+  } else {
+    CHK(s.flags.ensure(16));
+    if (d_idx) {
+      CHK(s.rec_z.ensure(RecoverLaunch::z_bytes()));
+      CHK(ensure_cell_table(c, s.stream));
+    }
+    CHK(ensure_ntt_table(c, s.stream));
+    CHK(begin_job(s));
+    HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, s.stream));
+    uint32_t* err = s.flags.template as<uint32_t>() + 1;
+    if (d_idx)
+      RecoverLaunch::recover(s.stream, d_idx, (uint32_t)k, (const uint8_t*)d_in, (uint32_t)nb, c->cell_table.p,
+                             c->ntt_table.p, s.rec_z.p, (uint8_t*)d_out, err);
+    else
+      RecoverLaunch::compute(s.stream, (const uint8_t*)d_in, (uint32_t)nb, c->ntt_table.p, (uint8_t*)d_out, err);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, s.stream));
+    CHK(end_job(s));
+  }
+  s.pending = true;
+  s.partial_job = true;
+  s.partial_of = 0;
+  s.msm_job = false;
+  s.curve = 0;
+  return 0;
+}
+
+// The host form of both (idx == nullptr: compute_cells): [indices | input | output] in slot 0's stage
+// buffer, the result copied back
+int cells_host(kzgmi_ctx* c, const uint64_t* idx, size_t k, const uint8_t* in, size_t nb, uint8_t* out) {
+  CHK(check_ctx(c));
+  CHK(check_cells_args(idx, k, in, nb, out, false));
+  CHK(slot0_idle(c));
+  if (nb == 0) return 0;
+  Slot& s = c->slots[0];
+  const size_t ib = (8 * k + 15) / 16 * 16, in_bytes = nb * (idx ? k * CellLaunch::BYTES : BlobLaunch::BYTES);
+  const size_t out_bytes = nb * RecoverLaunch::OUT_BYTES;
+  CHK(s.stage.ensure(ib + in_bytes + out_bytes));
+  uint8_t* di = s.stage.template as<uint8_t>();
+  uint8_t* din = di + ib;
+  uint8_t* dout = din + in_bytes;
+  hipStream_t cs = c->h2d_stream;
+  if (s.done_rec) HIPCHK(hipStreamWaitEvent(cs, s.done_ev, 0));  // the stage buffer is free
+  if (idx) CHK(h2d(s, cs, di, idx, 8 * k));
+  CHK(h2d(s, cs, din, in, in_bytes));
+  CHK(add_dep(s, cs));  // the job's kernels wait for its copy only
+  CHK(enqueue_cells_job(c, s, idx ? di : nullptr, k, din, nb, dout));
+  CHK(finish_slot(c, s, nullptr));
+  HIPCHK(hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+int kzgmi_compute_cells_device_async(kzgmi_ctx* c, int slot, const void* d_blobs, size_t nb, void* d_cells_out) {
+  KZ_ROUTE(c, nullptr, slot);
+  CHK(check_ctx(c, slot));
+  CHK(check_cells_args(nullptr, 0, d_blobs, nb, d_cells_out, true));
+  Roctx rx("kzgmi_compute_cells_device_async");
+  return enqueue_cells_job(c, c->slots[slot], nullptr, 0, d_blobs, nb, d_cells_out);
+}
+
+int kzgmi_compute_cells_device(kzgmi_ctx* c, const void* d_blobs, size_t nb, void* d_cells_out) {
+  CHK(check_ctx(c));
+  CHK(slot0_idle(c));
+  CHK(kzgmi_compute_cells_device_async(c, 0, d_blobs, nb, d_cells_out));
+  return kzgmi_slot_wait(c, 0, nullptr);
+}
+
+int kzgmi_compute_cells(kzgmi_ctx* c, const uint8_t* blobs, size_t nb, uint8_t* cells_out) {
+  return cells_host(c, nullptr, 0, blobs, nb, cells_out);
+}
+
+int kzgmi_recover_cells_device_async(kzgmi_ctx* c, int slot, const void* d_cell_indices, size_t k, const void* d_cells,
+                                     size_t nb, void* d_cells_out) {
+  KZ_ROUTE(c, nullptr, slot);
+  CHK(check_ctx(c, slot));
+  if (!d_cell_indices) return fail(KZGMI_ERR_ARG, "null argument");
+  CHK(check_cells_args(d_cell_indices, k, d_cells, nb, d_cells_out, true));
+  Roctx rx("kzgmi_recover_cells_device_async");
+  return enqueue_cells_job(c, c->slots[slot], d_cell_indices, k, d_cells, nb, d_cells_out);
+}
+
+int kzgmi_recover_cells_device(kzgmi_ctx* c, const void* d_cell_indices, size_t k, const void* d_cells, size_t nb,
+                               void* d_cells_out) {
+  CHK(check_ctx(c));
+  CHK(slot0_idle(c));
+  CHK(kzgmi_recover_cells_device_async(c, 0, d_cell_indices, k, d_cells, nb, d_cells_out));
+  return kzgmi_slot_wait(c, 0, nullptr);
+}
+
+int kzgmi_recover_cells(kzgmi_ctx* c, const uint64_t* cell_indices, size_t k, const uint8_t* cells, size_t nb,
+                        uint8_t* cells_out) {
+  if (!cell_indices) return fail(KZGMI_ERR_ARG, "null argument");
+  return cells_host(c, cell_indices, k, cells, nb, cells_out);
 }
 
 int kzgmi_g1_compress_device(kzgmi_ctx* c, kzgmi_curve curve, const void* d_points, size_t n, void* d_out) {

@@ -153,6 +153,22 @@ struct CellLaunch {
                               void* pow, uint32_t* chal_out);
 };
 
+// ---- EIP-7594 cell extension and recovery (recover.hpp, launch_recover.hip): BLS12-381 only
+struct RecoverLaunch {
+  static constexpr size_t OUT_BYTES = 8192 * 32;    // one extended blob: 128 cells
+  static constexpr uint32_t MIN_CELLS = 64, MAX_CELLS = 128;
+  static size_t table_bytes();                      // the transform table: twiddles and scale factors
+  static size_t z_bytes();                          // recover's per-call table (vanishing polynomial values, cell places)
+  static void table(hipStream_t st, void* table);
+  // blob b -> its 128 cells at out + b * OUT_BYTES; every element range-checked
+  static void compute(hipStream_t st, const uint8_t* blobs, uint32_t nb, const void* table, uint8_t* out, uint32_t* err);
+  // the k given cells of every blob (cells: nb x k x 2048 B, in the order of the k shared indices)
+  // -> all 128; an index >= 128, a duplicate or an inconsistent blob raises DERR_ARG, an element
+  // >= r DERR_SCALAR.  cell_table: CellLaunch's coset table; z: z_bytes() of scratch
+  static void recover(hipStream_t st, const void* cell_indices, uint32_t k, const uint8_t* cells, uint32_t nb,
+                      const void* cell_table, const void* table, void* z, uint8_t* out, uint32_t* err);
+};
+
 inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace kzgmi

@@ -109,6 +109,12 @@ def lib():
         "kzgmi_verify_cell_batch": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, u8p, ip], c.c_int),
         "kzgmi_verify_cell_batch_device": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, u8p, ip], c.c_int),
         "kzgmi_verify_cell_batch_device_async": ([vp, vp, c.c_int, vp, sz, vp, vp, vp, vp, sz, u8p], c.c_int),
+        "kzgmi_compute_cells": ([vp, vp, sz, vp], c.c_int),
+        "kzgmi_compute_cells_device": ([vp, vp, sz, vp], c.c_int),
+        "kzgmi_compute_cells_device_async": ([vp, c.c_int, vp, sz, vp], c.c_int),
+        "kzgmi_recover_cells": ([vp, vp, sz, vp, sz, vp], c.c_int),
+        "kzgmi_recover_cells_device": ([vp, vp, sz, vp, sz, vp], c.c_int),
+        "kzgmi_recover_cells_device_async": ([vp, c.c_int, vp, sz, vp, sz, vp], c.c_int),
         "kzgmi_slot_wait": ([vp, c.c_int, ip], c.c_int),
         "kzgmi_last_combination": ([vp, u8p, u8p], c.c_int),
         "kzgmi_msm_g1": ([vp, c.c_int, vp, vp, sz, u8p], c.c_int),
@@ -171,6 +177,8 @@ def exported_symbols():
         "kzgmi_verify_blob_batch", "kzgmi_verify_blob_batch_device", "kzgmi_verify_blob_batch_device_async",
         "kzgmi_cell_srs_load", "kzgmi_cell_srs_free", "kzgmi_cell_batch_challenge_device", "kzgmi_cell_interp_device",
         "kzgmi_verify_cell_batch", "kzgmi_verify_cell_batch_device", "kzgmi_verify_cell_batch_device_async",
+        "kzgmi_compute_cells", "kzgmi_compute_cells_device", "kzgmi_compute_cells_device_async",
+        "kzgmi_recover_cells", "kzgmi_recover_cells_device", "kzgmi_recover_cells_device_async",
     ]
 
 
@@ -183,6 +191,7 @@ ERR_NOT_IN_SUBGROUP = -7
 FS_CHUNK = 4096
 BLOB_BYTES = 4096 * 32  # an EIP-4844 blob: 4096 big-endian canonical Fr elements
 CELL_BYTES = 64 * 32    # an EIP-7594 cell: 64 big-endian canonical Fr elements
+EXT_BLOB_BYTES = 128 * CELL_BYTES  # the 128 cells of one blob
 CELLS_PER_EXT_BLOB = 128
 
 
@@ -790,6 +799,86 @@ class Context:
         self._order(slot)
         _check(lib().kzgmi_verify_cell_batch_device_async(self.handle, h, int(slot), *ptrs, int(n), _r32(r)))
 
+    # ------------------------------------------------------------------ EIP-7594 cell extension / recovery
+    @staticmethod
+    def _device_indices(cell_indices, like):
+        """(tensor, k): the uint64 cell indices on `like`'s device (a device tensor is taken as it is)."""
+        if _is_device_tensor(cell_indices):
+            return cell_indices, cell_indices.numel() * cell_indices.element_size() // 8
+        import torch
+        raw = _u64_bytes(cell_indices)
+        return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(like.device), len(raw) // 8
+
+    def compute_cells(self, blobs, n: Optional[int] = None, out=None):
+        """compute_cells (the cells only, no proofs): n blobs (n x 128 KiB) -> their 128 cells each
+        (n x 256 KiB, cell i of blob b at byte 262144 b + 2048 i).  Device tensor in: a device tensor
+        out (`out` if given); host buffer in: bytes out."""
+        if _is_device_tensor(blobs):
+            import torch
+            if n is None:
+                n = blobs.numel() * blobs.element_size() // BLOB_BYTES
+            if out is None:
+                out = torch.empty(n * EXT_BLOB_BYTES, dtype=torch.uint8, device=blobs.device)
+            pb, po = _dptr(blobs, n * BLOB_BYTES), _dptr(out, n * EXT_BLOB_BYTES)
+            self._order(0)
+            _check(lib().kzgmi_compute_cells_device(self.handle, pb, int(n), po))
+            return out
+        pb, lb, kb = _host_ptr(blobs)
+        if n is None:
+            n = lb // BLOB_BYTES
+        if lb < n * BLOB_BYTES:
+            raise ValueError("input buffer shorter than n blobs")
+        buf = ctypes.create_string_buffer(max(1, n * EXT_BLOB_BYTES))
+        _check(lib().kzgmi_compute_cells(self.handle, pb, int(n), ctypes.addressof(buf)))
+        del kb
+        return buf.raw[:n * EXT_BLOB_BYTES]
+
+    def compute_cells_async(self, slot: int, blobs, n: int, out):
+        """Enqueue compute_cells of device tensors on `slot`; wait(slot) completes it (and raises
+        its device-side errors)."""
+        pb, po = _dptr(blobs, n * BLOB_BYTES), _dptr(out, n * EXT_BLOB_BYTES)
+        self._order(slot)
+        _check(lib().kzgmi_compute_cells_device_async(self.handle, int(slot), pb, int(n), po))
+
+    def recover_cells(self, cell_indices, cells, n_blobs: Optional[int] = None, out=None):
+        """The cells of recover_cells_and_kzg_proofs for n_blobs blobs that share their k cell indices
+        (64 <= k <= 128, distinct, any order): cells holds n_blobs x k cells, blob after blob, each
+        blob's in the order of the indices.  Returns all 128 cells of every blob (n_blobs x 256 KiB).
+        Inconsistent cells (no polynomial of degree < 4096 takes them all) raise KzgmiError
+        (KZGMI_ERR_ARG).  Device tensor in: a device tensor out; host buffer in: bytes out."""
+        if _is_device_tensor(cells):
+            import torch
+            idx, k = self._device_indices(cell_indices, cells)
+            if n_blobs is None:
+                n_blobs = cells.numel() * cells.element_size() // (CELL_BYTES * k) if k else 0
+            if out is None:
+                out = torch.empty(n_blobs * EXT_BLOB_BYTES, dtype=torch.uint8, device=cells.device)
+            pi, pc = _dptr(idx, 8 * k), _dptr(cells, n_blobs * k * CELL_BYTES)
+            po = _dptr(out, n_blobs * EXT_BLOB_BYTES)
+            self._order(0)
+            _check(lib().kzgmi_recover_cells_device(self.handle, pi, int(k), pc, int(n_blobs), po))
+            return out
+        raw = _u64_bytes(cell_indices)
+        k = len(raw) // 8
+        (pi, li, ki), (pc, lc, kc) = _host_ptr(raw), _host_ptr(cells)
+        if n_blobs is None:
+            n_blobs = lc // (CELL_BYTES * k) if k else 0
+        if lc < n_blobs * k * CELL_BYTES:
+            raise ValueError("input buffer shorter than n_blobs x k cells")
+        buf = ctypes.create_string_buffer(max(1, n_blobs * EXT_BLOB_BYTES))
+        _check(lib().kzgmi_recover_cells(self.handle, pi, int(k), pc, int(n_blobs), ctypes.addressof(buf)))
+        del ki, kc
+        return buf.raw[:n_blobs * EXT_BLOB_BYTES]
+
+    def recover_cells_async(self, slot: int, cell_indices, cells, n_blobs: int, out):
+        """Enqueue recover_cells of device tensors on `slot` (cell_indices: a device tensor of k
+        uint64, kept alive by the caller until wait(slot)); wait(slot) completes it."""
+        k = cell_indices.numel() * cell_indices.element_size() // 8
+        pi, pc = _dptr(cell_indices, 8 * k), _dptr(cells, n_blobs * k * CELL_BYTES)
+        po = _dptr(out, n_blobs * EXT_BLOB_BYTES)
+        self._order(slot)
+        _check(lib().kzgmi_recover_cells_device_async(self.handle, int(slot), pi, int(k), pc, int(n_blobs), po))
+
     def wait(self, slot: int) -> bool:
         ok = ctypes.c_int(-1)
         try:
@@ -1039,6 +1128,17 @@ def verify_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs:
         raise KzgmiError(-1, "not a cell SRS (Context.load_cell_srs)")
     return srs.ctx.verify_cell_batch(srs, b"".join(unique), cidx, list(cell_indices), b"".join(bytes(x) for x in cells),
                                      b"".join(bytes(p) for p in proofs_bytes), m=len(unique), n=n, r=r)
+
+
+def compute_cells(blobs, n: Optional[int] = None, ctx: Optional[Context] = None):
+    """EIP-7594 compute_cells on the GPU: the 128 cells of every blob (Context.compute_cells)."""
+    return (ctx or default_context()).compute_cells(blobs, n)
+
+
+def recover_cells(cell_indices, cells, n_blobs: Optional[int] = None, ctx: Optional[Context] = None):
+    """The cells of EIP-7594 recover_cells_and_kzg_proofs on the GPU for blobs that share their cell
+    indices (Context.recover_cells)."""
+    return (ctx or default_context()).recover_cells(cell_indices, cells, n_blobs)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:
