@@ -65,7 +65,9 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * whole batches per device through the async entry points (kzgmi_slot_device).  6: the EIP-4844
  * blob entry points kzgmi_blob_*_device and kzgmi_verify_blob_batch* were added; still 6 (additive):
  * the EIP-7594 cell entry points kzgmi_cell_* and kzgmi_verify_cell_batch*, and the cell extension
- * and recovery entry points kzgmi_compute_cells* and kzgmi_recover_cells*.  A caller built
+ * and recovery entry points kzgmi_compute_cells* and kzgmi_recover_cells*, and the cell proof entry
+ * points kzgmi_cell_pk_*, kzgmi_*_cells_and_proofs*, kzgmi_fk20_scalars_device, kzgmi_g1_fft128_device.
+ * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
 
@@ -348,7 +350,7 @@ int kzgmi_verify_cell_batch_device_async(kzgmi_ctx* ctx, const kzgmi_cell_srs* s
                                          size_t n, const uint8_t* r32);
 
 /* ---- EIP-7594 cell extension and recovery (compute_cells, and the cells of
- * recover_cells_and_kzg_proofs; cell PROOFS are not generated) -- BLS12-381 only, with the cell
+ * recover_cells_and_kzg_proofs; the proofs: the next section) -- BLS12-381 only, with the cell
  * conventions above.  A blob is 4096 x 32 B big-endian canonical Fr, blob[k] = p(dom[k]) with
  * dom[k] = (w^2)^rev12(k) and deg p < 4096; its 128 cells are 8192 x 32 B = 256 KiB, cell i at byte
  * 2048 i.  An input element >= r: KZGMI_ERR_SCALAR.
@@ -377,6 +379,59 @@ int kzgmi_recover_cells_device(kzgmi_ctx* ctx, const void* d_cell_indices, size_
                                void* d_cells_out);
 int kzgmi_recover_cells_device_async(kzgmi_ctx* ctx, int slot, const void* d_cell_indices, size_t k,
                                      const void* d_cells, size_t nb, void* d_cells_out);
+
+/* ---- EIP-7594 cell proof generation (compute_cells_and_kzg_proofs, recover_cells_and_kzg_proofs),
+ * the FK20 way -- BLS12-381 only, with the cell conventions above.  For a blob with polynomial
+ * p(X) = sum_{j < 4096} c_j X^j and z_i = h_i^64,
+ *     proof_i = [q_i(tau)]_1,   q_i(X) = (p(X) - I_i(X)) / (X^64 - z_i) = floor(p / (X^64 - z_i))
+ * (I_i = p mod (X^64 - z_i): cell i's interpolation polynomial), 48 B ZCash compressed (infinity:
+ * 0xC0 and 47 zero bytes); proof i of blob b at byte 48 (128 b + i) of proofs_out.
+ * With omega = w^64 (order 128) and S_m = [tau^m]_1:  proof_i = P_{rev7(i)},
+ * P_e = sum_{t < 63} omega^(e t) H_t,  H_t = sum_{b < 64} sum_{u <= 62 - t} c_{64 (u + t + 1) + b} S_{64 u + b}.
+ * H is computed as 64 cyclic convolutions of length 128: a^(b) = (c_b, c_{64 + b}, .., c_{64 63 + b},
+ * 0 x 64), x^(b)[0] = S_b, x^(b)[128 - u] = S_{64 u + b} for u = 1 .. 62 and infinity elsewhere;
+ * hhat[pos] = sum_b DFT(a^(b))[pos] DFT(x^(b))[pos] and H_t = IDFT(hhat)[t + 1] (root omega).
+ * The cell proof key holds DFT(x^(b)) for every b -- 8192 points that depend on the SRS only -- as a
+ * fixed-base window table (kzgmi_cell_pk_device_bytes: about 0.5 GiB).  g1_monomial: [tau^m]_1 for
+ * m < 4096, 4096 x 96 B, validated like kzgmi_cell_srs_load's points (encoding, on curve, in G1, each
+ * with its own error code; the point at infinity: KZGMI_ERR_ARG).  The key lives on the context's
+ * primary device and works with that device's slots only, as commit keys do; a key of another
+ * context: KZGMI_ERR_ARG.
+ * compute_cells_and_proofs: cells_out may be NULL (proofs only); otherwise its bytes are those of
+ * kzgmi_compute_cells.  recover_cells_and_proofs: kzgmi_recover_cells (cells_out is required),
+ * then the proofs of every recovered blob; an inconsistent input fails with KZGMI_ERR_ARG exactly as
+ * kzgmi_recover_cells does.  No proof is written by a call that fails.
+ * Semantics, errors and sizes otherwise follow kzgmi_compute_cells* / kzgmi_recover_cells*
+ * (element >= r: KZGMI_ERR_SCALAR; nb == 0 succeeds and writes nothing; nb > 4096: KZGMI_ERR_ARG;
+ * 16-byte aligned device arrays; outputs overlap neither the inputs nor each other; async forms
+ * complete with kzgmi_slot_wait).  Scratch lives in the slot's workspace. */
+typedef struct kzgmi_cell_pk kzgmi_cell_pk;
+int kzgmi_cell_pk_load(kzgmi_ctx* ctx, const uint8_t* g1_monomial, kzgmi_cell_pk** out);
+void kzgmi_cell_pk_free(kzgmi_cell_pk* pk);
+size_t kzgmi_cell_pk_device_bytes(const kzgmi_cell_pk* pk);
+int kzgmi_compute_cells_and_proofs(kzgmi_ctx* ctx, const kzgmi_cell_pk* pk, const uint8_t* blobs, size_t nb,
+                                   uint8_t* cells_out, uint8_t* proofs_out);
+int kzgmi_compute_cells_and_proofs_device(kzgmi_ctx* ctx, const kzgmi_cell_pk* pk, const void* d_blobs, size_t nb,
+                                          void* d_cells_out, void* d_proofs_out);
+int kzgmi_compute_cells_and_proofs_device_async(kzgmi_ctx* ctx, const kzgmi_cell_pk* pk, int slot,
+                                                const void* d_blobs, size_t nb, void* d_cells_out,
+                                                void* d_proofs_out);
+int kzgmi_recover_cells_and_proofs(kzgmi_ctx* ctx, const kzgmi_cell_pk* pk, const uint64_t* cell_indices, size_t k,
+                                   const uint8_t* cells, size_t nb, uint8_t* cells_out, uint8_t* proofs_out);
+int kzgmi_recover_cells_and_proofs_device(kzgmi_ctx* ctx, const kzgmi_cell_pk* pk, const void* d_cell_indices,
+                                          size_t k, const void* d_cells, size_t nb, void* d_cells_out,
+                                          void* d_proofs_out);
+int kzgmi_recover_cells_and_proofs_device_async(kzgmi_ctx* ctx, const kzgmi_cell_pk* pk, int slot,
+                                                const void* d_cell_indices, size_t k, const void* d_cells,
+                                                size_t nb, void* d_cells_out, void* d_proofs_out);
+/* Diagnostics (synchronous, slot 0), like kzgmi_cell_interp_device.
+ * fk20_scalars: DFT(a^(b))[pos] of nb device-resident blobs as 32 B big-endian at
+ * 32 ((128 blob + pos) 64 + b) of d_out (nb x 256 KiB).
+ * g1_fft128: count (<= 4096) independent size-128 DFTs over G1 of uncompressed points (96 B each,
+ * validated: encoding, on curve), natural order in and out, root omega; inverse != 0: root omega^-1
+ * and the factor 1 / 128. */
+int kzgmi_fk20_scalars_device(kzgmi_ctx* ctx, const void* d_blobs, size_t nb, void* d_out);
+int kzgmi_g1_fft128_device(kzgmi_ctx* ctx, const void* d_points96, size_t count, int inverse, void* d_out96);
 
 /* Validate n device-resident G1 encodings (flags: KZGMI_FLAG_COMPRESSED,
  * KZGMI_FLAG_SUBGROUP_CHECK): 0 if all are valid, else the first error class found. */

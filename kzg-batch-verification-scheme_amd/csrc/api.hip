@@ -108,6 +108,7 @@ struct Slot {
                                                  // cell batches: z_k = h_k^64 and y_k = 0
   DevBuf cell_part, cell_coef;                   // cell batches: per-coset coefficients; -c_m (64 x 8 LE words)
   DevBuf rec_z;                                  // recover_cells: the call's vanishing-polynomial table (recover.hpp)
+  DevBuf fk_coef, fk_scal, fk_a, fk_b, fk_enc;   // cell proofs (fk20.hpp): coefficients, ahat, two point vectors, encodings
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -136,7 +137,8 @@ struct Slot {
     DevBuf* bufs[] = {&pts, &inf, &scal_r, &scal_s, &scal_t, &tpart, &cnt, &off, &coarse, &ent, &total, &sval, &skey,
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
-                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z};
+                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z,
+                      &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc};
     for (DevBuf* b : bufs) f(*b);
   }
 };
@@ -144,6 +146,7 @@ struct Slot {
 }  // namespace
 
 struct kzgmi_cell_srs;
+struct kzgmi_cell_pk;
 
 struct kzgmi_ctx {
   int device = 0;
@@ -241,6 +244,7 @@ struct kzgmi_ctx {
   std::vector<kzgmi_srs*> srs_list;  // live SRS objects: detached (device memory freed) on destroy
   std::vector<kzgmi_ck*> ck_list;    // live commit keys: same
   std::vector<kzgmi_cell_srs*> cell_srs_list;  // live cell SRS objects: same (their inner kzgmi_srs is in srs_list)
+  std::vector<kzgmi_cell_pk*> cell_pk_list;    // live cell proof keys: same
 };
 
 // prover commit key: rows w = 0..15 of 2^(16 w)-shifted SRS points, [row][point] Montgomery affine
@@ -269,6 +273,13 @@ struct kzgmi_cell_srs {
   DevBuf pts;                       // [tau^m]_1, m < 64, Montgomery affine, then their images phi([tau^m]_1) (GLV)
   DevBuf inf;                       // the 128 infinity bytes (all zero: checked at load)
   std::vector<kzgmi_cell_srs*> peers;  // multi-device context: the same SRS on each peer device
+};
+
+// EIP-7594 cell proof key (fk20.hpp): xhat, the transforms of the monomial SRS, as a table of window multiples
+struct kzgmi_cell_pk {
+  kzgmi_ctx* ctx = nullptr;
+  DevBuf tab;                       // [base][window][multiple] Montgomery affine
+  DevBuf tab_inf;                   // per base: xhat[base] is the point at infinity
 };
 
 namespace {
@@ -1448,6 +1459,11 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
     cs->pts.release();
     cs->inf.release();
     cs->ctx = nullptr;
+  }
+  for (kzgmi_cell_pk* pk : c->cell_pk_list) {  // detach: later kzgmi_cell_pk_free() only deletes the struct
+    pk->tab.release();
+    pk->tab_inf.release();
+    pk->ctx = nullptr;
   }
   for (kzgmi_ck* ck : c->ck_list) {  // detach: later kzgmi_ck_free() only deletes the struct
     ck->pts.release();
@@ -2920,6 +2936,295 @@ int kzgmi_recover_cells(kzgmi_ctx* c, const uint64_t* cell_indices, size_t k, co
                         uint8_t* cells_out) {
   if (!cell_indices) return fail(KZGMI_ERR_ARG, "null argument");
   return cells_host(c, cell_indices, k, cells, nb, cells_out);
+}
+
+// ------------------------------------------------------------------------------ EIP-7594 cell proofs (FK20)
+}  // extern "C"
+namespace {
+constexpr size_t kFftMax = 4096;  // transforms per kzgmi_g1_fft128_device call
+
+// The argument checks every proof form shares; d_idx == nullptr: compute (in: nb blobs, the cells
+// optional), else recover (in: nb x k cells, the cells required)
+int check_proofs_args(const void* d_idx, size_t k, const void* d_in, size_t nb, const void* d_cells,
+                      const void* d_proofs, bool device) {
+  if (d_idx || d_cells) {
+    CHK(check_cells_args(d_idx, k, d_in, nb, d_cells, device));
+  } else {
+    if (nb > kRecoverMaxBlobs) return fail(KZGMI_ERR_ARG, "too many blobs (max 4096 per call)");
+    if (nb && !d_in) return fail(KZGMI_ERR_ARG, "null argument");
+  }
+  if (nb && !d_proofs) return fail(KZGMI_ERR_ARG, "null argument");
+  if (!device || nb == 0) return 0;
+  if (((uintptr_t)d_in | (uintptr_t)d_proofs) & 15) return fail(KZGMI_ERR_ARG, "device arrays must be 16-byte aligned");
+  const size_t in_bytes = nb * (d_idx ? k * CellLaunch::BYTES : BlobLaunch::BYTES), pf = nb * Fk20Launch::PROOFS_BYTES;
+  if (ranges_overlap(d_in, in_bytes, d_proofs, pf) || (d_idx && ranges_overlap(d_idx, 8 * k, d_proofs, pf)) ||
+      (d_cells && ranges_overlap(d_cells, nb * RecoverLaunch::OUT_BYTES, d_proofs, pf)))
+    return fail(KZGMI_ERR_ARG, "the output overlaps an input or the other output");
+  return 0;
+}
+
+// One proof job on slot s (any slot of the key's device): like enqueue_cells_job, followed by the
+// FK20 pipeline on the blobs (compute) or on the first half of every recovered blob (recover)
+int enqueue_proofs_job(kzgmi_ctx* c, Slot& s, const kzgmi_cell_pk* pk, const void* d_idx, size_t k, const void* d_in,
+                       size_t nb, void* d_cells, void* d_proofs) {
+  using L = Launch<Bls12_381>;
+  using XY = Xyzz<Bls12_381>;
+  if (s.pending) return fail(KZGMI_ERR_ARG, "slot busy: call kzgmi_slot_wait first");
+  if (nb == 0) {  // succeeds, writes nothing
+    CHK(sync_slot(s));  // host_flags may still be the target of a copy
+    s.host_flags[0] = 1;
+    s.host_flags[1] = 0;
+  } else {
+    const uint32_t n = (uint32_t)nb, np = n * Fk20Launch::N;
+    CHK(s.flags.ensure(16));
+    CHK(s.fk_coef.ensure(Fk20Launch::coef_bytes(n)));
+    CHK(s.fk_scal.ensure(Fk20Launch::scal_bytes(n)));
+    CHK(s.fk_a.ensure((size_t)np * sizeof(XY)));
+    CHK(s.fk_b.ensure((size_t)np * sizeof(XY)));
+    CHK(s.fk_enc.ensure((size_t)np * (96 + 48)));
+    if (d_idx) {
+      CHK(s.rec_z.ensure(RecoverLaunch::z_bytes()));
+      CHK(ensure_cell_table(c, s.stream));
+    }
+    CHK(ensure_ntt_table(c, s.stream));
+    CHK(begin_job(s));
+    hipStream_t st = s.stream;
+    HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, st));
+    uint32_t* err = s.flags.template as<uint32_t>() + 1;
+    const uint8_t* blobs = (const uint8_t*)d_in;
+    size_t stride = BlobLaunch::BYTES;
+    if (d_idx) {
+      RecoverLaunch::recover(st, d_idx, (uint32_t)k, (const uint8_t*)d_in, n, c->cell_table.p, c->ntt_table.p,
+                             s.rec_z.p, (uint8_t*)d_cells, err);
+      blobs = (const uint8_t*)d_cells;  // cells 0..63 are the blob's bytes
+      stride = RecoverLaunch::OUT_BYTES;
+    } else if (d_cells) {
+      RecoverLaunch::compute(st, blobs, n, c->ntt_table.p, (uint8_t*)d_cells, err);
+    }
+    uint8_t* scal = s.fk_scal.template as<uint8_t>();
+    XY* a = s.fk_a.template as<XY>();
+    XY* b = s.fk_b.template as<XY>();
+    uint8_t* enc = s.fk_enc.template as<uint8_t>();
+    uint8_t* enc48 = enc + (size_t)np * 96;
+    Fk20Launch::scalars(st, blobs, stride, n, c->ntt_table.p, true, s.fk_coef.p, scal, err);
+    Fk20Launch::msm(st, scal, n, pk->tab.p, pk->tab_inf.template as<uint8_t>(), a);
+    Fk20Launch::fft(st, a, n, c->ntt_table.p, true);
+    Fk20Launch::shift(st, a, n, b);
+    Fk20Launch::fft(st, b, n, c->ntt_table.p, false);
+    L::encode_points(st, b, np, enc);
+    L::compress_points(st, enc, np, enc48);
+    Fk20Launch::emit(st, enc48, (size_t)np * 48, err, d_proofs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, st));
+    CHK(end_job(s));
+  }
+  s.pending = true;
+  s.partial_job = true;
+  s.partial_of = 0;
+  s.msm_job = false;
+  s.curve = 0;
+  return 0;
+}
+
+int check_cell_pk(const kzgmi_ctx* c, const kzgmi_cell_pk* pk) {
+  if (!pk || std::find(c->cell_pk_list.begin(), c->cell_pk_list.end(), pk) == c->cell_pk_list.end())
+    return fail(KZGMI_ERR_ARG, "not a cell proof key of this context (kzgmi_cell_pk_load)");
+  return 0;
+}
+
+// The host form of both (idx == nullptr: compute): [indices | input | cells | proofs] in slot 0's
+// stage buffer, the results copied back
+int proofs_host(kzgmi_ctx* c, const kzgmi_cell_pk* pk, const uint64_t* idx, size_t k, const uint8_t* in, size_t nb,
+                uint8_t* cells_out, uint8_t* proofs_out) {
+  CHK(check_ctx(c));
+  CHK(check_cell_pk(c, pk));
+  CHK(check_proofs_args(idx, k, in, nb, cells_out, proofs_out, false));
+  CHK(slot0_idle(c));
+  if (nb == 0) return 0;
+  Slot& s = c->slots[0];
+  const size_t ib = (8 * k + 15) / 16 * 16, in_bytes = nb * (idx ? k * CellLaunch::BYTES : BlobLaunch::BYTES);
+  const size_t cell_bytes = cells_out ? nb * RecoverLaunch::OUT_BYTES : 0, pf = nb * Fk20Launch::PROOFS_BYTES;
+  CHK(s.stage.ensure(ib + in_bytes + cell_bytes + pf));
+  uint8_t* di = s.stage.template as<uint8_t>();
+  uint8_t* din = di + ib;
+  uint8_t* dcells = din + in_bytes;
+  uint8_t* dpf = dcells + cell_bytes;
+  hipStream_t cs = c->h2d_stream;
+  if (s.done_rec) HIPCHK(hipStreamWaitEvent(cs, s.done_ev, 0));  // the stage buffer is free
+  if (idx) CHK(h2d(s, cs, di, idx, 8 * k));
+  CHK(h2d(s, cs, din, in, in_bytes));
+  CHK(add_dep(s, cs));  // the job's kernels wait for its copy only
+  CHK(enqueue_proofs_job(c, s, pk, idx ? di : nullptr, k, din, nb, cells_out ? dcells : nullptr, dpf));
+  CHK(finish_slot(c, s, nullptr));
+  if (cells_out) HIPCHK(hipMemcpy(cells_out, dcells, cell_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(proofs_out, dpf, pf, hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+void kzgmi_cell_pk_free(kzgmi_cell_pk* pk) {
+  if (!pk) return;
+  if (kzgmi_ctx* c = pk->ctx) {
+    (void)hipSetDevice(c->device);
+    auto& v = c->cell_pk_list;
+    v.erase(std::remove(v.begin(), v.end(), pk), v.end());
+    pk->tab.release();
+    pk->tab_inf.release();
+  }
+  delete pk;
+}
+
+size_t kzgmi_cell_pk_device_bytes(const kzgmi_cell_pk* pk) { return pk ? pk->tab.cap + pk->tab_inf.cap : 0; }
+
+int kzgmi_cell_pk_load(kzgmi_ctx* c, const uint8_t* g1_monomial, kzgmi_cell_pk** out) {
+  CHK(check_ctx(c));
+  if (!g1_monomial || !out) return fail(KZGMI_ERR_ARG, "null cell proof key argument");
+  *out = nullptr;
+  CHK(slot0_idle(c));
+  using Cv = Bls12_381;
+  using L = Launch<Cv>;
+  using XY = Xyzz<Cv>;
+  constexpr uint32_t T = Fk20Launch::SRS_POINTS;
+  Slot& s = c->slots[0];
+  CHK(ensure_ntt_table(c, s.stream));
+  kzgmi_cell_pk* pk = new kzgmi_cell_pk();
+  DevBuf pts, inf, x;  // the validated SRS and the 64 vectors x^(b): needed while the table is built
+  auto undo = [&](int rc) {
+    pts.release();
+    inf.release();
+    x.release();
+    pk->tab.release();
+    pk->tab_inf.release();
+    delete pk;
+    return rc;
+  };
+  int r = 0;
+  if ((r = s.stage.ensure(T * 96)) || (r = s.flags.ensure(16)) || (r = pts.ensure(T * sizeof(Affine<Cv>))) ||
+      (r = inf.ensure(T)) || (r = x.ensure((size_t)Fk20Launch::KEY_TRANSFORMS * Fk20Launch::N * sizeof(XY))) ||
+      (r = pk->tab.ensure(Fk20Launch::table_bytes())) || (r = pk->tab_inf.ensure(Fk20Launch::table_flags())) ||
+      (r = begin_job(s)))
+    return undo(r);
+  hipStream_t st = s.stream;
+  std::vector<uint8_t> inf_h(T);
+  bool okk = hipMemcpyAsync(s.stage.p, g1_monomial, T * 96, hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemsetAsync(s.flags.p, 0, 16, st) == hipSuccess;
+  if (okk) {  // validated like any input point, and in G1 (the table's rows rely on the order r)
+    uint32_t* err = s.flags.template as<uint32_t>() + 1;
+    Affine<Cv>* p = pts.template as<Affine<Cv>>();
+    L::convert_points(st, s.stage.template as<uint8_t>(), T, p, inf.template as<uint8_t>(), err);
+    L::subgroup_check(st, p, inf.template as<uint8_t>(), T, err);
+    Fk20Launch::key(st, p, c->ntt_table.p, x.template as<XY>(), pk->tab.p, pk->tab_inf.template as<uint8_t>());
+    okk = hipGetLastError() == hipSuccess &&
+          hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(inf_h.data(), inf.p, T, hipMemcpyDeviceToHost, st) == hipSuccess && sync_job(s) == 0;
+  }
+  if (!okk) return undo(fail(KZGMI_ERR_DEVICE, "cell proof key upload/precompute failed"));
+  int e = map_device_err((uint32_t)s.host_flags[1]);
+  for (uint32_t k = 0; !e && k < T; ++k)
+    if (inf_h[k]) e = fail(KZGMI_ERR_ARG, "cell SRS G1 element is the point at infinity");
+  if (e) return undo(e);
+  pts.release();
+  inf.release();
+  x.release();
+  pk->ctx = c;
+  c->cell_pk_list.push_back(pk);
+  *out = pk;
+  return 0;
+}
+
+int kzgmi_compute_cells_and_proofs_device_async(kzgmi_ctx* c, const kzgmi_cell_pk* pk, int slot, const void* d_blobs,
+                                                size_t nb, void* d_cells_out, void* d_proofs_out) {
+  KZ_ROUTE(c, nullptr, slot);  // (proof keys live on the primary device: its slots only)
+  CHK(check_ctx(c, slot));
+  CHK(check_cell_pk(c, pk));
+  CHK(check_proofs_args(nullptr, 0, d_blobs, nb, d_cells_out, d_proofs_out, true));
+  Roctx rx("kzgmi_compute_cells_and_proofs_device_async");
+  return enqueue_proofs_job(c, c->slots[slot], pk, nullptr, 0, d_blobs, nb, d_cells_out, d_proofs_out);
+}
+
+int kzgmi_compute_cells_and_proofs_device(kzgmi_ctx* c, const kzgmi_cell_pk* pk, const void* d_blobs, size_t nb,
+                                          void* d_cells_out, void* d_proofs_out) {
+  CHK(check_ctx(c));
+  CHK(slot0_idle(c));
+  CHK(kzgmi_compute_cells_and_proofs_device_async(c, pk, 0, d_blobs, nb, d_cells_out, d_proofs_out));
+  return kzgmi_slot_wait(c, 0, nullptr);
+}
+
+int kzgmi_compute_cells_and_proofs(kzgmi_ctx* c, const kzgmi_cell_pk* pk, const uint8_t* blobs, size_t nb,
+                                   uint8_t* cells_out, uint8_t* proofs_out) {
+  return proofs_host(c, pk, nullptr, 0, blobs, nb, cells_out, proofs_out);
+}
+
+int kzgmi_recover_cells_and_proofs_device_async(kzgmi_ctx* c, const kzgmi_cell_pk* pk, int slot,
+                                                const void* d_cell_indices, size_t k, const void* d_cells, size_t nb,
+                                                void* d_cells_out, void* d_proofs_out) {
+  KZ_ROUTE(c, nullptr, slot);
+  CHK(check_ctx(c, slot));
+  CHK(check_cell_pk(c, pk));
+  if (!d_cell_indices) return fail(KZGMI_ERR_ARG, "null argument");
+  CHK(check_proofs_args(d_cell_indices, k, d_cells, nb, d_cells_out, d_proofs_out, true));
+  Roctx rx("kzgmi_recover_cells_and_proofs_device_async");
+  return enqueue_proofs_job(c, c->slots[slot], pk, d_cell_indices, k, d_cells, nb, d_cells_out, d_proofs_out);
+}
+
+int kzgmi_recover_cells_and_proofs_device(kzgmi_ctx* c, const kzgmi_cell_pk* pk, const void* d_cell_indices, size_t k,
+                                          const void* d_cells, size_t nb, void* d_cells_out, void* d_proofs_out) {
+  CHK(check_ctx(c));
+  CHK(slot0_idle(c));
+  CHK(kzgmi_recover_cells_and_proofs_device_async(c, pk, 0, d_cell_indices, k, d_cells, nb, d_cells_out, d_proofs_out));
+  return kzgmi_slot_wait(c, 0, nullptr);
+}
+
+int kzgmi_recover_cells_and_proofs(kzgmi_ctx* c, const kzgmi_cell_pk* pk, const uint64_t* cell_indices, size_t k,
+                                   const uint8_t* cells, size_t nb, uint8_t* cells_out, uint8_t* proofs_out) {
+  if (!cell_indices) return fail(KZGMI_ERR_ARG, "null argument");
+  return proofs_host(c, pk, cell_indices, k, cells, nb, cells_out, proofs_out);
+}
+
+int kzgmi_fk20_scalars_device(kzgmi_ctx* c, const void* d_blobs, size_t nb, void* d_out) {
+  CHK(check_ctx(c));
+  if (nb && (!d_blobs || !d_out)) return fail(KZGMI_ERR_ARG, "null argument");
+  if (nb > kRecoverMaxBlobs) return fail(KZGMI_ERR_ARG, "too many blobs (max 4096 per call)");
+  if (((uintptr_t)d_blobs | (uintptr_t)d_out) & 15) return fail(KZGMI_ERR_ARG, "device arrays must be 16-byte aligned");
+  CHK(slot0_idle(c));
+  CHK(ensure_ntt_table(c, c->slots[0].stream));
+  return cell_slot0_job(c, [&](Slot& s, uint32_t* err) -> int {
+    CHK(s.fk_coef.ensure(Fk20Launch::coef_bytes((uint32_t)nb)));
+    Fk20Launch::scalars(s.stream, (const uint8_t*)d_blobs, BlobLaunch::BYTES, (uint32_t)nb, c->ntt_table.p, false,
+                        s.fk_coef.p, (uint8_t*)d_out, err);
+    return 0;
+  });
+}
+
+int kzgmi_g1_fft128_device(kzgmi_ctx* c, const void* d_points96, size_t count, int inverse, void* d_out96) {
+  CHK(check_ctx(c));
+  if (count && (!d_points96 || !d_out96)) return fail(KZGMI_ERR_ARG, "null argument");
+  if (count > kFftMax) return fail(KZGMI_ERR_ARG, "too many transforms (max 4096 per call)");
+  if (((uintptr_t)d_points96 | (uintptr_t)d_out96) & 15) return fail(KZGMI_ERR_ARG, "device arrays must be 16-byte aligned");
+  CHK(slot0_idle(c));
+  CHK(ensure_ntt_table(c, c->slots[0].stream));
+  using Cv = Bls12_381;
+  using L = Launch<Cv>;
+  using XY = Xyzz<Cv>;
+  return cell_slot0_job(c, [&](Slot& s, uint32_t* err) -> int {
+    const uint32_t cnt = (uint32_t)count, n = cnt * Fk20Launch::N;
+    if (!n) return 0;
+    CHK(s.pts.ensure((size_t)n * sizeof(Affine<Cv>)));
+    CHK(s.inf.ensure(n));
+    CHK(s.fk_a.ensure((size_t)n * sizeof(XY)));
+    CHK(s.fk_b.ensure((size_t)n * sizeof(XY)));
+    hipStream_t st = s.stream;
+    XY* a = s.fk_a.template as<XY>();
+    XY* b = s.fk_b.template as<XY>();
+    L::convert_points(st, (const uint8_t*)d_points96, n, s.pts.template as<Affine<Cv>>(), s.inf.template as<uint8_t>(), err);
+    Fk20Launch::from_affine(st, s.pts.template as<Affine<Cv>>(), s.inf.template as<uint8_t>(), n, a);
+    Fk20Launch::fft(st, a, cnt, c->ntt_table.p, inverse != 0);
+    if (inverse) Fk20Launch::scale128(st, a, n);
+    Fk20Launch::unrev(st, a, cnt, b);
+    L::encode_points(st, b, n, (uint8_t*)d_out96);
+    return 0;
+  });
 }
 
 int kzgmi_g1_compress_device(kzgmi_ctx* c, kzgmi_curve curve, const void* d_points, size_t n, void* d_out) {

@@ -169,6 +169,37 @@ struct RecoverLaunch {
                       const void* cell_table, const void* table, void* z, uint8_t* out, uint32_t* err);
 };
 
+// ---- EIP-7594 cell proof generation, FK20 (fk20.hpp, launch_fk20.hip): BLS12-381 only
+struct Fk20Launch {
+  using XY = Xyzz<Bls12_381>;
+  using AF = Affine<Bls12_381>;
+  static constexpr uint32_t SRS_POINTS = 4096;      // [tau^m]_1, m < 4096 (m < 4032 is used)
+  static constexpr uint32_t N = 128;                // transform size = proofs per blob
+  static constexpr uint32_t KEY_TRANSFORMS = 64;    // xhat: one transform per column b
+  static constexpr size_t PROOFS_BYTES = 128 * 48;  // one blob's proofs, compressed
+  static size_t table_bytes();                      // the key's window table (affine rows)
+  static size_t table_flags();                      // its infinity flags: one byte per base
+  static size_t coef_bytes(uint32_t nb);            // c_m / 2^k, standard form
+  static size_t scal_bytes(uint32_t nb);            // ahat: 8192 x 32 B per blob
+  // the validated monomial SRS -> table, tab_inf; x: KEY_TRANSFORMS * N records of scratch
+  static void key(hipStream_t st, const AF* srs, const void* ntt_table, XY* x, void* table, uint8_t* tab_inf);
+  // ahat of nb blobs `stride` bytes apart -> scal (32 B big-endian at 32 ((128 blob + pos) 64 + b)),
+  // times 1 / 128 if fold128 (the pipeline's inverse transform is then unscaled); every element
+  // range-checked
+  static void scalars(hipStream_t st, const uint8_t* blobs, size_t stride, uint32_t nb, const void* ntt_table,
+                      bool fold128, void* coef, uint8_t* scal, uint32_t* err);
+  static void msm(hipStream_t st, const uint8_t* scal, uint32_t nb, const void* table, const uint8_t* tab_inf, XY* out);
+  // count transforms of 128 records in place, natural order in, bit-reversed order out; the
+  // inverse is not scaled by 1 / 128
+  static void fft(hipStream_t st, XY* data, uint32_t count, const void* ntt_table, bool inverse);
+  static void scale128(hipStream_t st, XY* data, uint32_t n);
+  static void shift(hipStream_t st, const XY* h, uint32_t count, XY* d);
+  static void unrev(hipStream_t st, const XY* in, uint32_t count, XY* out);
+  static void from_affine(hipStream_t st, const AF* pts, const uint8_t* inf, uint32_t n, XY* out);
+  // out = in (bytes: a multiple of 16) unless *err is set
+  static void emit(hipStream_t st, const void* in, size_t bytes, const uint32_t* err, void* out);
+};
+
 inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace kzgmi

@@ -115,6 +115,17 @@ def lib():
         "kzgmi_recover_cells": ([vp, vp, sz, vp, sz, vp], c.c_int),
         "kzgmi_recover_cells_device": ([vp, vp, sz, vp, sz, vp], c.c_int),
         "kzgmi_recover_cells_device_async": ([vp, c.c_int, vp, sz, vp, sz, vp], c.c_int),
+        "kzgmi_cell_pk_load": ([vp, u8p, c.POINTER(vp)], c.c_int),
+        "kzgmi_cell_pk_free": ([vp], None),
+        "kzgmi_cell_pk_device_bytes": ([vp], sz),
+        "kzgmi_compute_cells_and_proofs": ([vp, vp, vp, sz, vp, vp], c.c_int),
+        "kzgmi_compute_cells_and_proofs_device": ([vp, vp, vp, sz, vp, vp], c.c_int),
+        "kzgmi_compute_cells_and_proofs_device_async": ([vp, vp, c.c_int, vp, sz, vp, vp], c.c_int),
+        "kzgmi_recover_cells_and_proofs": ([vp, vp, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_recover_cells_and_proofs_device": ([vp, vp, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_recover_cells_and_proofs_device_async": ([vp, vp, c.c_int, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_fk20_scalars_device": ([vp, vp, sz, vp], c.c_int),
+        "kzgmi_g1_fft128_device": ([vp, vp, sz, c.c_int, vp], c.c_int),
         "kzgmi_slot_wait": ([vp, c.c_int, ip], c.c_int),
         "kzgmi_last_combination": ([vp, u8p, u8p], c.c_int),
         "kzgmi_msm_g1": ([vp, c.c_int, vp, vp, sz, u8p], c.c_int),
@@ -179,6 +190,11 @@ def exported_symbols():
         "kzgmi_verify_cell_batch", "kzgmi_verify_cell_batch_device", "kzgmi_verify_cell_batch_device_async",
         "kzgmi_compute_cells", "kzgmi_compute_cells_device", "kzgmi_compute_cells_device_async",
         "kzgmi_recover_cells", "kzgmi_recover_cells_device", "kzgmi_recover_cells_device_async",
+        "kzgmi_cell_pk_load", "kzgmi_cell_pk_free", "kzgmi_cell_pk_device_bytes",
+        "kzgmi_compute_cells_and_proofs", "kzgmi_compute_cells_and_proofs_device",
+        "kzgmi_compute_cells_and_proofs_device_async", "kzgmi_recover_cells_and_proofs",
+        "kzgmi_recover_cells_and_proofs_device", "kzgmi_recover_cells_and_proofs_device_async",
+        "kzgmi_fk20_scalars_device", "kzgmi_g1_fft128_device",
     ]
 
 
@@ -193,6 +209,7 @@ BLOB_BYTES = 4096 * 32  # an EIP-4844 blob: 4096 big-endian canonical Fr element
 CELL_BYTES = 64 * 32    # an EIP-7594 cell: 64 big-endian canonical Fr elements
 EXT_BLOB_BYTES = 128 * CELL_BYTES  # the 128 cells of one blob
 CELLS_PER_EXT_BLOB = 128
+PROOFS_BYTES = CELLS_PER_EXT_BLOB * 48  # the 128 compressed cell proofs of one blob
 
 
 def _flags(compressed: bool = False, subgroup_check: bool = False, fiat_shamir: bool = False,
@@ -378,6 +395,26 @@ def _r32(r):
     if r is None:
         return None
     return int(r).to_bytes(32, "big") if isinstance(r, int) else bytes(r)
+
+
+@dataclass
+class CellProofKey:
+    """EIP-7594 cell proof key: the FK20 transforms of [tau^m]_1, m < 4096, as a fixed-base window
+    table on the device (kzgmi_cell_pk_load)."""
+    ctx: "Context"
+    handle: ctypes.c_void_p
+
+    @property
+    def device_bytes(self) -> int:
+        return int(lib().kzgmi_cell_pk_device_bytes(self.handle)) if self.handle else 0
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().kzgmi_cell_pk_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
 
 
 class CommitKey:
@@ -879,6 +916,130 @@ class Context:
         self._order(slot)
         _check(lib().kzgmi_recover_cells_device_async(self.handle, int(slot), pi, int(k), pc, int(n_blobs), po))
 
+    # ------------------------------------------------------------------ EIP-7594 cell proofs (FK20)
+    def load_cell_proof_key(self, g1_monomial: bytes) -> CellProofKey:
+        """The cell proof key of g1_monomial = [tau^m]_1 for m < 4096 (4096 x 96 B)."""
+        if len(g1_monomial) != 4096 * 96:
+            raise ValueError("g1_monomial must hold 4096 uncompressed G1 points (393216 bytes)")
+        h = ctypes.c_void_p()
+        _check(lib().kzgmi_cell_pk_load(self.handle, bytes(g1_monomial), ctypes.byref(h)))
+        return CellProofKey(self, h)
+
+    @staticmethod
+    def _cell_pk_handle(pk):
+        if not isinstance(pk, CellProofKey):
+            raise KzgmiError(-1, "not a cell proof key (Context.load_cell_proof_key)")
+        return pk.handle
+
+    def compute_cells_and_proofs(self, pk: CellProofKey, blobs, n: Optional[int] = None, cells=True, out=None,
+                                 proofs_out=None):
+        """compute_cells_and_kzg_proofs: n blobs -> (cells, proofs): the cells of compute_cells (None
+        with cells=False) and the 128 compressed proofs of every blob (n x 6144 B, proof i of blob b at
+        byte 48 (128 b + i)).  Device tensor in: device tensors out (`out`, `proofs_out` if given);
+        host buffer in: bytes out."""
+        h = self._cell_pk_handle(pk)
+        if _is_device_tensor(blobs):
+            import torch
+            if n is None:
+                n = blobs.numel() * blobs.element_size() // BLOB_BYTES
+            if cells and out is None:
+                out = torch.empty(n * EXT_BLOB_BYTES, dtype=torch.uint8, device=blobs.device)
+            if proofs_out is None:
+                proofs_out = torch.empty(n * PROOFS_BYTES, dtype=torch.uint8, device=blobs.device)
+            pc = _dptr(out, n * EXT_BLOB_BYTES) if cells else None
+            pb, pp = _dptr(blobs, n * BLOB_BYTES), _dptr(proofs_out, n * PROOFS_BYTES)
+            self._order(0)
+            _check(lib().kzgmi_compute_cells_and_proofs_device(self.handle, h, pb, int(n), pc, pp))
+            return (out if cells else None), proofs_out
+        pb, lb, kb = _host_ptr(blobs)
+        if n is None:
+            n = lb // BLOB_BYTES
+        if lb < n * BLOB_BYTES:
+            raise ValueError("input buffer shorter than n blobs")
+        cbuf = ctypes.create_string_buffer(max(1, n * EXT_BLOB_BYTES)) if cells else None
+        pbuf = ctypes.create_string_buffer(max(1, n * PROOFS_BYTES))
+        _check(lib().kzgmi_compute_cells_and_proofs(self.handle, h, pb, int(n),
+                                                    ctypes.addressof(cbuf) if cells else None, ctypes.addressof(pbuf)))
+        del kb
+        return (cbuf.raw[:n * EXT_BLOB_BYTES] if cells else None), pbuf.raw[:n * PROOFS_BYTES]
+
+    def compute_cells_and_proofs_async(self, pk: CellProofKey, slot: int, blobs, n: int, out, proofs_out):
+        """Enqueue compute_cells_and_proofs of device tensors on `slot` (out None: proofs only);
+        wait(slot) completes it (and raises its device-side errors)."""
+        h = self._cell_pk_handle(pk)
+        pc = _dptr(out, n * EXT_BLOB_BYTES) if out is not None else None
+        pb, pp = _dptr(blobs, n * BLOB_BYTES), _dptr(proofs_out, n * PROOFS_BYTES)
+        self._order(slot)
+        _check(lib().kzgmi_compute_cells_and_proofs_device_async(self.handle, h, int(slot), pb, int(n), pc, pp))
+
+    def recover_cells_and_proofs(self, pk: CellProofKey, cell_indices, cells, n_blobs: Optional[int] = None, out=None,
+                                 proofs_out=None):
+        """recover_cells_and_kzg_proofs: recover_cells, then the 128 proofs of every recovered blob ->
+        (cells, proofs).  Inconsistent cells raise KzgmiError (KZGMI_ERR_ARG) as recover_cells does.
+        Device tensor in: device tensors out; host buffer in: bytes out."""
+        h = self._cell_pk_handle(pk)
+        if _is_device_tensor(cells):
+            import torch
+            idx, k = self._device_indices(cell_indices, cells)
+            if n_blobs is None:
+                n_blobs = cells.numel() * cells.element_size() // (CELL_BYTES * k) if k else 0
+            if out is None:
+                out = torch.empty(n_blobs * EXT_BLOB_BYTES, dtype=torch.uint8, device=cells.device)
+            if proofs_out is None:
+                proofs_out = torch.empty(n_blobs * PROOFS_BYTES, dtype=torch.uint8, device=cells.device)
+            pi, pc = _dptr(idx, 8 * k), _dptr(cells, n_blobs * k * CELL_BYTES)
+            po, pp = _dptr(out, n_blobs * EXT_BLOB_BYTES), _dptr(proofs_out, n_blobs * PROOFS_BYTES)
+            self._order(0)
+            _check(lib().kzgmi_recover_cells_and_proofs_device(self.handle, h, pi, int(k), pc, int(n_blobs), po, pp))
+            return out, proofs_out
+        raw = _u64_bytes(cell_indices)
+        k = len(raw) // 8
+        (pi, li, ki), (pc, lc, kc) = _host_ptr(raw), _host_ptr(cells)
+        if n_blobs is None:
+            n_blobs = lc // (CELL_BYTES * k) if k else 0
+        if lc < n_blobs * k * CELL_BYTES:
+            raise ValueError("input buffer shorter than n_blobs x k cells")
+        cbuf = ctypes.create_string_buffer(max(1, n_blobs * EXT_BLOB_BYTES))
+        pbuf = ctypes.create_string_buffer(max(1, n_blobs * PROOFS_BYTES))
+        _check(lib().kzgmi_recover_cells_and_proofs(self.handle, h, pi, int(k), pc, int(n_blobs),
+                                                    ctypes.addressof(cbuf), ctypes.addressof(pbuf)))
+        del ki, kc
+        return cbuf.raw[:n_blobs * EXT_BLOB_BYTES], pbuf.raw[:n_blobs * PROOFS_BYTES]
+
+    def recover_cells_and_proofs_async(self, pk: CellProofKey, slot: int, cell_indices, cells, n_blobs: int, out,
+                                       proofs_out):
+        """Enqueue recover_cells_and_proofs of device tensors on `slot` (cell_indices: a device tensor
+        of k uint64, kept alive by the caller until wait(slot)); wait(slot) completes it."""
+        h = self._cell_pk_handle(pk)
+        k = cell_indices.numel() * cell_indices.element_size() // 8
+        pi, pc = _dptr(cell_indices, 8 * k), _dptr(cells, n_blobs * k * CELL_BYTES)
+        po, pp = _dptr(out, n_blobs * EXT_BLOB_BYTES), _dptr(proofs_out, n_blobs * PROOFS_BYTES)
+        self._order(slot)
+        _check(lib().kzgmi_recover_cells_and_proofs_device_async(self.handle, h, int(slot), pi, int(k), pc,
+                                                                 int(n_blobs), po, pp))
+
+    def fk20_scalars(self, blobs, n: int, out=None):
+        """Diagnostic: the Fr stage of the proof pipeline for n device-resident blobs: DFT(a^(b))[pos]
+        as 32 B big-endian at 32 ((128 blob + pos) 64 + b) of a device tensor of n x 256 KiB."""
+        import torch
+        if out is None:
+            out = torch.empty(n * EXT_BLOB_BYTES, dtype=torch.uint8, device=blobs.device)
+        pb, po = _dptr(blobs, n * BLOB_BYTES), _dptr(out, n * EXT_BLOB_BYTES)
+        self._order(0)
+        _check(lib().kzgmi_fk20_scalars_device(self.handle, pb, int(n), po))
+        return out
+
+    def g1_fft128(self, points, count: int, inverse: bool = False, out=None):
+        """Diagnostic: `count` independent size-128 DFTs over G1 of device-resident uncompressed points
+        (96 B each), natural order in and out, root w^64 (inverse: its inverse and 1 / 128)."""
+        import torch
+        if out is None:
+            out = torch.empty(count * 128 * 96, dtype=torch.uint8, device=points.device)
+        pi, po = _dptr(points, count * 128 * 96), _dptr(out, count * 128 * 96)
+        self._order(0)
+        _check(lib().kzgmi_g1_fft128_device(self.handle, pi, int(count), 1 if inverse else 0, po))
+        return out
+
     def wait(self, slot: int) -> bool:
         ok = ctypes.c_int(-1)
         try:
@@ -1139,6 +1300,16 @@ def recover_cells(cell_indices, cells, n_blobs: Optional[int] = None, ctx: Optio
     """The cells of EIP-7594 recover_cells_and_kzg_proofs on the GPU for blobs that share their cell
     indices (Context.recover_cells)."""
     return (ctx or default_context()).recover_cells(cell_indices, cells, n_blobs)
+
+
+def compute_cells_and_proofs(pk: CellProofKey, blobs, n: Optional[int] = None, cells=True):
+    """Context.compute_cells_and_proofs on the key's context."""
+    return pk.ctx.compute_cells_and_proofs(pk, blobs, n, cells)
+
+
+def recover_cells_and_proofs(pk: CellProofKey, cell_indices, cells, n_blobs: Optional[int] = None):
+    """Context.recover_cells_and_proofs on the key's context."""
+    return pk.ctx.recover_cells_and_proofs(pk, cell_indices, cells, n_blobs)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:
