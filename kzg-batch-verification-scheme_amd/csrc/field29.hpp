@@ -11,7 +11,9 @@
 // accumulator, so a limb product is ONE v_mad_u64_u32: 2N^2 mads + ~4 column ops x (2N - 1)
 // (BLS12-381 392 mads instead of 288 x 2 + column moves; BN254 162 instead of 128 x 2).
 // Additions and subtractions pay a carry pass instead (sub29: a + B - b with B a multiple of p
-// whose limbs are biased into [2^29, 2^30), so no limb goes negative).  Measured in one harness
+// whose limbs are biased into [2^29, 2^30), so no limb goes negative) -- unless the subtraction
+// follows a product directly: mulsub29 / sqrsub3_29 add its limbs inside the product's high
+// columns, which mask and shift every result limb anyway.  Measured in one harness
 // (tools/probes/radix29/acc29.hip): the BLS12-381 mixed addition runs 1.17-1.22x faster than
 // the 32-bit lazy form, and it fits 108 VGPRs without spills.
 //
@@ -115,10 +117,67 @@ KZ_DEV void vs_run(uint64_t& acc, const uint32_t (&m)[Q::N]) {
   (void)cc;
 }
 
-// column K of (a b [+ c d] + m p): low columns produce m_K, high ones the result limbs
-template <class Q, bool TWO, int K>
+// The m p run of a high column with one more term in front: acc += e, a 32-bit addend, as a
+// v_mad_u64_u32 by the constant 1 in the run's first statement (no asm statement of its own,
+// so no s_nop pad of its own).  The fused product-and-subtract forms below pass the limb of
+// B - x that a sub29 pass after the product would have added.
+template <class Q, int K, int I, int CNT>
+KZ_DEV void vs_run_add(uint64_t& acc, const uint32_t (&m)[Q::N], uint32_t e) {
+  uint64_t cc;
+  if constexpr (CNT >= 3) {
+    asm("v_mad_u64_u32 %0, %1, %2, 1, %0\n\tv_mad_u64_u32 %0, %1, %3, %4, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %5, %6, %0\n\tv_mad_u64_u32 %0, %1, %7, %8, %0"
+        : "+v"(acc), "=&s"(cc)
+        : "v"(e), "v"(m[I]), "s"(Q::MOD[K - I]), "v"(m[I + 1]), "s"(Q::MOD[K - I - 1]), "v"(m[I + 2]),
+          "s"(Q::MOD[K - I - 2]));
+    vs_run<Q, K, I + 3, CNT - 3>(acc, m);
+  } else if constexpr (CNT == 2) {
+    asm("v_mad_u64_u32 %0, %1, %2, 1, %0\n\tv_mad_u64_u32 %0, %1, %3, %4, %0\n\t"
+        "v_mad_u64_u32 %0, %1, %5, %6, %0"
+        : "+v"(acc), "=&s"(cc)
+        : "v"(e), "v"(m[I]), "s"(Q::MOD[K - I]), "v"(m[I + 1]), "s"(Q::MOD[K - I - 1]));
+  } else {
+    static_assert(CNT == 1, "every high column has an m p term");
+    asm("v_mad_u64_u32 %0, %1, %2, 1, %0\n\tv_mad_u64_u32 %0, %1, %3, %4, %0"
+        : "+v"(acc), "=&s"(cc)
+        : "v"(e), "v"(m[I]), "s"(Q::MOD[K - I]));
+  }
+  (void)cc;
+}
+
+// What a product's high columns add besides the limb products: nothing, or limb by limb the
+// B - x (Sub29) or C - s - 2t (Sub3_29) of a subtraction that rides on the product's own mask
+// and shift instead of paying a carry pass after it.  limb(i), i < N - 1, is non-negative and
+// below 2^30 / 2^31 under the preconditions of sub29 / sub3_29 (biased B, C; x, s, t
+// normalised); top() is the top limb's term in 32-bit wrap-around arithmetic, as in sub29 -- a
+// biased multiple of p can have a smaller top limb than the subtrahend, only the total is
+// non-negative.  The bias limbs are compile-time constants (literal operands of the v_sub).
+struct NoSub29 {
+  static constexpr bool ON = false;
+};
+template <class Q>
+struct Sub29 {
+  static constexpr bool ON = true;
+  const F29<Q>& x;
+  const uint32_t (&B)[Q::N];
+  KZ_DEV uint32_t limb(int i) const { return B[i] - x.v[i]; }
+  KZ_DEV uint32_t top() const { return B[Q::N - 1] - x.v[Q::N - 1]; }
+};
+template <class Q>
+struct Sub3_29 {
+  static constexpr bool ON = true;
+  const F29<Q>& s;
+  const F29<Q>& t;
+  const uint32_t (&C)[Q::N];
+  KZ_DEV uint32_t limb(int i) const { return C[i] - (s.v[i] + t.v[i] + t.v[i]); }
+  KZ_DEV uint32_t top() const { return C[Q::N - 1] - (s.v[Q::N - 1] + t.v[Q::N - 1] + t.v[Q::N - 1]); }
+};
+
+// column K of (a b [+ c d] + m p): low columns produce m_K, high ones the result limbs (plus
+// the subtraction's limb, SUB)
+template <class Q, bool TWO, int K, class SUB>
 KZ_DEV void mont29_cols(uint64_t& acc, uint32_t (&m)[Q::N], F29<Q>& t, const F29<Q>& a, const F29<Q>& b,
-                        const F29<Q>& c, const F29<Q>& d) {
+                        const F29<Q>& c, const F29<Q>& d, const SUB& sub) {
   constexpr int N = Q::N;
   if constexpr (K < N) {
     if constexpr (K == 0) acc = (uint64_t)a.v[0] * b.v[0];  // compiler's mad with a 0 addend: no zeroed pair
@@ -128,20 +187,22 @@ KZ_DEV void mont29_cols(uint64_t& acc, uint32_t (&m)[Q::N], F29<Q>& t, const F29
     m[K] = ((uint32_t)acc * Q::INV) & M29;
     mad29s(acc, m[K], Q::MOD[0]);  // low 29 bits become 0
     acc >>= 29;
-    mont29_cols<Q, TWO, K + 1>(acc, m, t, a, b, c, d);
+    mont29_cols<Q, TWO, K + 1>(acc, m, t, a, b, c, d, sub);
   } else if constexpr (K < 2 * N - 1) {
     vv_run<K, K - N + 1, 2 * N - 1 - K>(acc, a.v, b.v);
     if constexpr (TWO) vv_run<K, K - N + 1, 2 * N - 1 - K>(acc, c.v, d.v);
-    vs_run<Q, K, K - N + 1, 2 * N - 1 - K>(acc, m);
+    if constexpr (SUB::ON) vs_run_add<Q, K, K - N + 1, 2 * N - 1 - K>(acc, m, sub.limb(K - N));
+    else vs_run<Q, K, K - N + 1, 2 * N - 1 - K>(acc, m);
     t.v[K - N] = (uint32_t)acc & M29;
     acc >>= 29;
-    mont29_cols<Q, TWO, K + 1>(acc, m, t, a, b, c, d);
+    mont29_cols<Q, TWO, K + 1>(acc, m, t, a, b, c, d, sub);
   }
 }
 
 // column K of a^2 + m p: off-diagonal a2_i a_{K-i} (i < K - i), the diagonal, m p
-template <class Q, int K>
-KZ_DEV void sqr29_cols(uint64_t& acc, uint32_t (&m)[Q::N], F29<Q>& t, const uint32_t (&a2)[Q::N], const F29<Q>& a) {
+template <class Q, int K, class SUB>
+KZ_DEV void sqr29_cols(uint64_t& acc, uint32_t (&m)[Q::N], F29<Q>& t, const uint32_t (&a2)[Q::N], const F29<Q>& a,
+                       const SUB& sub) {
   constexpr int N = Q::N;
   if constexpr (K < 2 * N - 1) {
     constexpr int lo = K < N ? 0 : K - N + 1;
@@ -154,40 +215,59 @@ KZ_DEV void sqr29_cols(uint64_t& acc, uint32_t (&m)[Q::N], F29<Q>& t, const uint
       m[K] = ((uint32_t)acc * Q::INV) & M29;
       mad29s(acc, m[K], Q::MOD[0]);
     } else {
-      vs_run<Q, K, K - N + 1, 2 * N - 1 - K>(acc, m);
+      if constexpr (SUB::ON) vs_run_add<Q, K, K - N + 1, 2 * N - 1 - K>(acc, m, sub.limb(K - N));
+      else vs_run<Q, K, K - N + 1, 2 * N - 1 - K>(acc, m);
       t.v[K - N] = (uint32_t)acc & M29;
     }
     acc >>= 29;
-    sqr29_cols<Q, K + 1>(acc, m, t, a2, a);
+    sqr29_cols<Q, K + 1>(acc, m, t, a2, a, sub);
   }
 }
 
 // (a b [+ c d] + m p) / R29 -- product scanning, one 64-bit accumulator per column
-template <class Q, bool TWO>
-KZ_DEV F29<Q> mont29(const F29<Q>& a, const F29<Q>& b, const F29<Q>& c, const F29<Q>& d) {
+template <class Q, bool TWO, class SUB = NoSub29>
+KZ_DEV F29<Q> mont29(const F29<Q>& a, const F29<Q>& b, const F29<Q>& c, const F29<Q>& d, const SUB& sub = SUB{}) {
   uint32_t m[Q::N];
   F29<Q> t;
   uint64_t acc = 0;
-  mont29_cols<Q, TWO, 0>(acc, m, t, a, b, c, d);
-  t.v[Q::N - 1] = (uint32_t)acc;
+  mont29_cols<Q, TWO, 0>(acc, m, t, a, b, c, d, sub);
+  if constexpr (SUB::ON) t.v[Q::N - 1] = (uint32_t)acc + sub.top();
+  else t.v[Q::N - 1] = (uint32_t)acc;
   return t;
 }
 template <class Q>
 KZ_DEV F29<Q> mul29(const F29<Q>& a, const F29<Q>& b) { return mont29<Q, false>(a, b, a, b); }
+// a b / R29 + B - x, the same integer in the same normal form as sub29(mul29(a, b), x, B) (limbs
+// 0..N-2 below 2^29 are the integer mod 2^(29 (N - 1)), the top limb the rest), without sub29's
+// carry pass: 2 VALU per limb (v_sub, v_mad_u64_u32) instead of 4.  Column bound: the product's
+// columns stay below 2^63 (mul2_29 below is the worst case the 64-bit accumulator carries) and
+// the addend below 2^30; tools/gen_params29.py check_bounds asserts it per call site.
+template <class Q>
+KZ_DEV F29<Q> mulsub29(const F29<Q>& a, const F29<Q>& b, const F29<Q>& x, const uint32_t (&B)[Q::N]) {
+  return mont29<Q, false>(a, b, a, b, Sub29<Q>{x, B});
+}
 // a^2 / R29: the off-diagonal limb products once, against a pre-doubled operand (2 a_i < 2^30),
 // plus the squares on the diagonal -- 91 + 14 + 196 (m p) = 301 mads instead of 392.  Column
 // bound: 7 x 2^59 + 2^58 + 14 x 2^58 + carry < 2^63 (limbs < 2^29, top limb < 2^16).
-template <class Q>
-KZ_DEV F29<Q> sqr29(const F29<Q>& a) {
+template <class Q, class SUB = NoSub29>
+KZ_DEV F29<Q> sqr29(const F29<Q>& a, const SUB& sub = SUB{}) {
   constexpr int N = Q::N;
   uint32_t a2[N];
   _Pragma("unroll") for (int i = 0; i < N; ++i) a2[i] = a.v[i] + a.v[i];
   uint32_t m[N];
   F29<Q> t;
   uint64_t acc = 0;
-  sqr29_cols<Q, 0>(acc, m, t, a2, a);
-  t.v[N - 1] = (uint32_t)acc;
+  sqr29_cols<Q, 0>(acc, m, t, a2, a, sub);
+  if constexpr (SUB::ON) t.v[N - 1] = (uint32_t)acc + sub.top();
+  else t.v[N - 1] = (uint32_t)acc;
   return t;
+}
+// a^2 / R29 + C - s - 2t, the same integer in the same normal form as sub3_29(sqr29(a), s, t, C)
+// (the accumulation's X3 = R^2 - PPP - 2 Q2) without its carry pass: 3 VALU per limb instead of
+// 5; the addend is below 2^31 against sqr29's column bound of 2^63
+template <class Q>
+KZ_DEV F29<Q> sqrsub3_29(const F29<Q>& a, const F29<Q>& s, const F29<Q>& t, const uint32_t (&C)[Q::N]) {
+  return sqr29<Q>(a, Sub3_29<Q>{s, t, C});
 }
 
 template <class Q>

@@ -823,6 +823,17 @@ KZ_DEV Xyzz<Cv> x29_to32(const X29<Q>& a) {
   if (a.inf) return Xyzz<Cv>::inf();
   return {fp_from29<Q, P>(a.x), fp_from29<Q, P>(a.y), fp_from29<Q, P>(a.zz), fp_from29<Q, P>(a.zzz)};
 }
+// The subtractions that follow a product directly -- P = U2 - X1, R = S2 - Y1 and X3 = R^2 - PPP
+// - 2 Q2 of the mixed addition (acc_loop29) and of the record addition (x29_add) -- as fused
+// product-and-subtract forms (field29.hpp mulsub29, sqrsub3_29): the same integers in the same
+// normal form, without the carry pass (BLS12-381: 4528 -> 4450 VALU per mixed addition, k_accumulate
+// 5.24 -> 5.04 ms, pipelined 2^20 batches 188.9 -> 190.8/s, profiles/r07/).  Per curve: BN254
+// keeps the two-pass forms -- its loop loses as many VALU in proportion (2117 -> 2068) but its
+// alternated A/B stayed inside the run-to-run spread (91.0 vs 90.2/s at 2^22, spread 1.1;
+// profiles/r07/ab_fused_sub_bn254.txt), and what does not separate from noise is not kept.
+template <class Cv>
+constexpr bool kFusedSub = Cv::ID == 0;
+
 // 2a (dbl-2008-s-1, a = 0).  Inputs within the record bounds; outputs x < 5.1p, y, zz, zzz <
 // 1.01p on BLS12-381; on BN254 (R29 / p ~ 169) x < 5.2p, y < 1.5p, zz, zzz < 1.1p (the same steps
 // of tools/gen_params29.py check_bounds, asserted per curve by tests/test_gpu_field.py).
@@ -854,10 +865,10 @@ KZ_DEV X29<Q> x29_add(const X29<Q>& a, const X29<Q>& b) {
   using G = F29<Q>;
   if (a.inf) return b;
   if (b.inf) return a;
-  const G U1 = mul29(a.x, b.zz), U2 = mul29(b.x, a.zz);    // < 1.01p
-  const G S1 = mul29(a.y, b.zzz), S2 = mul29(b.y, a.zzz);
-  const G P = sub29(U2, U1, Q::B2);                         // < 3.02p
-  const G R = sub29(S2, S1, Q::B2);
+  const G U1 = mul29(a.x, b.zz), S1 = mul29(a.y, b.zzz);   // < 1.01p
+  // U2 - U1 and S2 - S1 ride on the products' own high columns (mulsub29), X3 below likewise
+  const G P = kFusedSub<Cv> ? mulsub29(b.x, a.zz, U1, Q::B2) : sub29(mul29(b.x, a.zz), U1, Q::B2);  // < 3.02p
+  const G R = kFusedSub<Cv> ? mulsub29(b.y, a.zzz, S1, Q::B2) : sub29(mul29(b.y, a.zzz), S1, Q::B2);
   if (is_zero29(P)) {
     if (is_zero29(R)) return x29_dbl<Q>(a);  // equal points (rare)
     return {G::zero(), G::zero(), G::zero(), G::zero(), true};
@@ -866,7 +877,7 @@ KZ_DEV X29<Q> x29_add(const X29<Q>& a, const X29<Q>& b) {
   const G PPP = mul29(P, PP);
   const G Q2 = mul29(U1, PP);
   X29<Q> o;
-  o.x = sub29(sqr29(R), add3_29(PPP, Q2, Q2), Q::B8);                           // < 9.1p
+  o.x = kFusedSub<Cv> ? sqrsub3_29(R, PPP, Q2, Q::C8) : sub29(sqr29(R), add3_29(PPP, Q2, Q2), Q::B8);  // < 9.1p
   o.y = mul2_29(R, sub29(Q2, o.x, Q::B16), S1, sub29(G::zero(), PPP, Q::B8));  // R (Q - X3) - S1 PPP
   o.zz = mul29(mul29(a.zz, b.zz), PP);
   o.zzz = mul29(mul29(a.zzz, b.zzz), PPP);
@@ -1027,10 +1038,9 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
         inf = false;
         continue;
       }
-      const G U2 = mul29(qx, ld(s_zz));
-      const G S2 = mul29(qy, ld(s_zzz));
-      const G P = sub29(U2, x, Q::ACC_P);  // BLS12-381 < 18p
-      const G R = sub29(S2, y, Q::ACC_R);  // BLS12-381 < 18p
+      // U2 - X1 and S2 - Y1 ride on the products' own high columns (mulsub29: no carry pass)
+      const G P = kFusedSub<Cv> ? mulsub29(qx, ld(s_zz), x, Q::ACC_P) : sub29(mul29(qx, ld(s_zz)), x, Q::ACC_P);  // BLS12-381 < 18p
+      const G R = kFusedSub<Cv> ? mulsub29(qy, ld(s_zzz), y, Q::ACC_R) : sub29(mul29(qy, ld(s_zzz)), y, Q::ACC_R);  // BLS12-381 < 18p
       if (is_zero29_mf(P)) {
         if (is_zero29_mf(R)) {
           dbl = true;
@@ -1044,7 +1054,8 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
       st(s_zz, mul29(ld(s_zz), PP));
       st(s_zzz, mul29(ld(s_zzz), PPP));
       const G Q2 = mul29(x, PP);
-      const G X3 = sub3_29(sqr29(R), PPP, Q2, Q::ACC_X3);  // one carry pass; BLS12-381 < 10p
+      // R^2 - PPP - 2 Q2, the subtraction in the square's high columns; BLS12-381 < 10p
+      const G X3 = kFusedSub<Cv> ? sqrsub3_29(R, PPP, Q2, Q::ACC_X3) : sub3_29(sqr29(R), PPP, Q2, Q::ACC_X3);
       // R (Q - X3) - Y1 PPP, with -PPP as ACC_PPP - PPP limb by limb (no carry pass; neg_lazy29)
       y = mul2_29(R, sub29(Q2, X3, Q::ACC_QX), y, neg_lazy29(PPP, Q::ACC_PPP));
       x = X3;

@@ -79,6 +79,18 @@ def check_bounds(p, n, nkp, roles):
     def mont2(a, b, c, d):
         assert max(a, b, c, d) < lim
         return (Fraction(a) * b + Fraction(c) * d) * p / R + 1
+    def fused(bias, k, sub):
+        # A subtraction fused into its product (field29.hpp mulsub29 / sqrsub3_29): high column K
+        # also adds the limb bias[K - n] - (the subtrahend's limbs).  The bias k p covers the
+        # subtrahend's bound `sub`; the addend is at most the bias limb (< 2^30, sub3_29's form
+        # < 2^31) and not negative (biased()/biased3() put every limb at or above what normalised
+        # subtrahend limbs reach); the column -- at most n limb products a_i b_j (or the square's
+        # pre-doubled off-diagonal ones) and n of m_i p_j, each below 2^58, the carry of the column
+        # before it (< 2^35) and the addend -- stays below 2^64.
+        assert k >= sub
+        addend = max(bias[:n - 1])
+        assert addend < 1 << 31
+        assert 2 * n * MASK * MASK + (1 << 35) + addend < 1 << 64, "fused column overflows"
     ro = {k: Fraction(v) for k, v in roles.items()}
     # points come out of a Montgomery product with canonical inputs (fp_to29, k_convert_points
     # <To29>): below (p / R29 + 1) p, NOT below p -- on BN254 that is 1.006 p, so negating q.y
@@ -100,10 +112,13 @@ def check_bounds(p, n, nkp, roles):
     for _ in range(50):
         U2, S2 = mont(qx, Z), mont(qy, Z)
         assert ro["ACC_P"] >= X and ro["ACC_R"] >= Y
+        fused(biased(roles["ACC_P"], p, n), ro["ACC_P"], X)   # P = mulsub29(q.x, zz, x)
+        fused(biased(roles["ACC_R"], p, n), ro["ACC_R"], Y)   # R = mulsub29(q.y, zzz, y)
         P, Rr = U2 + ro["ACC_P"], S2 + ro["ACC_R"]
         assert P < nkp and Rr < nkp, "zero test range"
         PP = mont(P, P); PPP = mont(P, PP); Q2 = mont(X, PP)
         assert ro["ACC_X3"] >= PPP + 2 * Q2
+        fused(biased3(roles["ACC_X3"], p, n), ro["ACC_X3"], PPP + 2 * Q2)  # X3 = sqrsub3_29(R, PPP, Q2)
         X3 = mont(Rr, Rr) + ro["ACC_X3"]
         assert ro["ACC_QX"] >= X3 and ro["ACC_PPP"] >= PPP
         # neg_lazy29 (ACC_PPP - PPP limb by limb, no carries): the top limb must not go negative
@@ -124,6 +139,8 @@ def check_bounds(p, n, nkp, roles):
     assert 2 >= U1 and 2 >= S1 and P < nkp and Rr < nkp
     PP = mont(P, P); PPP = mont(P, PP); Q2 = mont(U1, PP)
     assert 8 >= PPP + 2 * Q2
+    fused(biased(2, p, n), 2, max(U1, S1))          # x29_add's P and R (mulsub29, B2)
+    fused(biased3(8, p, n), 8, PPP + 2 * Q2)        # x29_add's X3 (sqrsub3_29, C8)
     X3 = mont(Rr, Rr) + 8
     assert 16 >= X3 and 8 >= PPP
     Y3 = mont2(Rr, Q2 + 16, S1, 8)
