@@ -1,6 +1,7 @@
 // Host-side launchers for every kernel, one set per curve.  Each group of launchers is
 // defined in its own translation unit (launch_*.hip) compiled once per curve (-DKZ_CURVE=0
-// BLS12-381, 1 BN254), so the device code builds in parallel; api.hip only calls these.
+// BLS12-381, 1 BN254), so the device code builds in parallel; the host units (api.hip,
+// host_*.hip) only call these.
 #pragma once
 #include "kernels.hpp"
 #include "msm_small.hpp"

@@ -89,7 +89,7 @@ constexpr int BINS_PER_SET = NBUCKETS >> COARSE_SHIFT;  // 256
 constexpr int TILE_TERMS = 4096;                        // terms per tile (16 per thread)
 // Window width c of a call (WBITS, NBUCKETS, BINS_PER_SET above are c = 16's): large calls use
 // c = 16; small ones (few entries per bucket) c = 13 -- 8x fewer buckets to reduce for 5/4 the
-// terms (api.hip call_wbits).  The sort, the window-sum reduction and the combination are
+// terms (host_core.hip call_wbits).  The sort, the window-sum reduction and the combination are
 // instantiated per c.
 template <int C>
 struct Win {
@@ -644,7 +644,7 @@ KZ_DEV Xyzz<Cv> load_xyzz(const Xyzz<Cv>* src) {
 // value in k_accumulate and k_fixup).  The host picks nthreads ~ (entry bound) / ACC_CHUNK(_SMALL),
 // capped at one resident round: the capped grid gives longer, equal chunks (fewer pieces, no
 // partial last round).
-// Work-queue form for calls whose grid reaches the cap (api.hip run_msm_core): ACC_QUEUE_FACTOR
+// Work-queue form for calls whose grid reaches the cap (host_core.hip run_msm_core): ACC_QUEUE_FACTOR
 // chunks per launched thread, none shorter than ACC_QUEUE_MIN_LEN entries.
 #ifndef KZ_ACC_QUEUE_FACTOR
 #define KZ_ACC_QUEUE_FACTOR 2
@@ -1074,7 +1074,7 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
 }
 
 // Waves per SIMD the accumulation is compiled for (VGPR budget 512 / waves per lane); the host
-// caps the grid at one resident round of CUs x 4 SIMDs x kAccWaves waves (api.hip).
+// caps the grid at one resident round of CUs x 4 SIMDs x kAccWaves waves (host_core.hip run_msm_core).
 // ZZ/ZZZ staged in LDS make 4 waves fit (the all-register 32-bit loop of round 1 needed 168
 // VGPRs: 7.53 vs 7.28 ms, profiles/r01/acc_lds_ab.txt); radix 2^29: 4 waves at 128 VGPRs once the rare doubling left the hot loop (7 VGPRs spilled outside it);
 // 3 waves / 167 VGPRs measured 6.94 vs 6.63 ms (profiles/r01/acc29_ab.txt).
@@ -1102,7 +1102,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAccWa
   // instead of a fill kernel between the two launches)
   if (crowd && blockIdx.x == 0 && threadIdx.x == 0) *crowd = 0u;
   // the entry range [lo, total) of this launch: the whole sorted list, or the sets of one MSM
-  // (api.hip run_msm_core's split accumulation; no bucket crosses a set boundary, so the range
+  // (host_core.hip run_msm_core's split accumulation; no bucket crosses a set boundary, so the range
   // end is where the last bucket ends)
   const uint32_t total = *total_p;
   const uint32_t lo = lo_p ? *lo_p : 0u;
@@ -1264,7 +1264,7 @@ __global__ void __launch_bounds__(256) k_fixup_crowded(const uint32_t* __restric
 }
 
 // Bucket stores of two accumulations over the same sets (the point ranges of a chunked
-// host-buffer batch, api.hip enqueue_batch_chunked): A[b] += B[b] where B's bucket is non-empty,
+// host-buffer batch, host_core.hip enqueue_batch_chunked): A[b] += B[b] where B's bucket is non-empty,
 // counts added (the reduction only tests them for zero); empty buckets' records are never read.
 template <class Cv>
 __global__ void __launch_bounds__(256) k_merge_buckets(uint32_t nb, uint32_t* __restrict__ acc29,
@@ -1292,7 +1292,7 @@ __global__ void __launch_bounds__(256) k_merge_buckets(uint32_t nb, uint32_t* __
 // doublings on the upper half's chain while the lower half idled: ~20 point operations per
 // wave instead of ~16; the kernel is latency-bound at 1.5 waves per SIMD.)
 // LOWP (the reduction and combination kernels): no raised issue priority -- the side stream of a
-// split accumulation runs them beside the critical-path accumulation (api.hip run_msm_core)
+// split accumulation runs them beside the critical-path accumulation (host_core.hip run_msm_core)
 template <class Cv, bool LOWP = false>
 __global__ void __launch_bounds__(256, 2) k_reduce_segments(uint32_t nseg, const uint32_t* __restrict__ cnt,
                                                          const uint32_t* __restrict__ acc29,
@@ -1324,7 +1324,7 @@ __global__ void __launch_bounds__(256, 2) k_reduce_segments(uint32_t nseg, const
 }
 
 // The same records from 4 threads per segment (lanes 4g .. 4g + 3), for calls with few bucket
-// sets -- the critical path of a split accumulation reduces only MSM#0's 8 sets (api.hip
+// sets -- the critical path of a split accumulation reduces only MSM#0's 8 sets (host_core.hip
 // run_msm_core), ~0.5 waves per SIMD with 2 threads per segment, so the segment's serial chain
 // sets the time.  Quarter h runs the running sums over buckets [4h, 4h + 4): r_h = sum_{i<4} i
 // S_{4h+i}, u_h = sum_{i<4} S_{4h+i}; then, with V_3 = u_3, V_2 = u_2 + u_3, V_1 = u_1 + V_2,

@@ -47,6 +47,30 @@ def test_no_device_fails_loudly():
     assert e.value.code == -5
 
 
+# one entry point per host unit (csrc/api.hip, host_batch, host_msm, host_eip, host_multi; host_core
+# defines none) and per feature family; each checks its context before anything else
+NULL_CTX_CALLS = ["kzgmi_ctx_reserve", "kzgmi_batch_verify_device", "kzgmi_msm_g1_device",
+                  "kzgmi_verify_blob_batch_device", "kzgmi_verify_cell_batch_device", "kzgmi_recover_cells_device",
+                  "kzgmi_compute_cells_and_proofs_device", "kzgmi_batch_verify_multi_device",
+                  "kzgmi_msm_g1_multi_device"]
+
+
+@pytest.mark.parametrize("name", NULL_CTX_CALLS)
+def test_null_context_error_is_shared_across_units(name):
+    """The host units share one last-error string: a null context is refused with KZGMI_ERR_ARG by
+    an entry point of every unit, and kzgmi_last_error(), which lives in api.hip, reports it.  A
+    unit with a last-error string of its own would leave the earlier message standing."""
+    import ctypes
+    import kzgmi
+    lib = kzgmi.lib()
+    # an earlier, different message (set by api.hip itself)
+    assert lib.kzgmi_host_alloc(0, None) == -1 and lib.kzgmi_last_error() == b"bad argument"
+    f = getattr(lib, name)
+    args = [None if issubclass(t, (ctypes.c_void_p, ctypes.c_char_p, ctypes._Pointer)) else 0 for t in f.argtypes]
+    assert f(*args) == -1  # KZGMI_ERR_ARG
+    assert lib.kzgmi_last_error() == b"null context"
+
+
 def test_shard_range():
     from kzgmi.distributed import shard_range
     for n in [0, 1, 7, 1 << 20, (1 << 20) + 3]:

@@ -162,7 +162,7 @@ def test_sharded_batch_cfg5_bn254(ctx):
 
 @pytest.mark.parametrize("curve,n,trusted", [("bls12_381", 300007, False), ("bls12_381", 262143, True),
                                              ("bn254", 524289, False),
-                                             # 2^15 < n <= 2^17: 13-bit windows (api.hip call_wbits)
+                                             # 2^15 < n <= 2^17: 13-bit windows (host_core.hip call_wbits)
                                              ("bls12_381", 100003, False), ("bls12_381", 70001, True),
                                              ("bn254", 90001, False)])
 def test_ragged_batch_vs_oracle(ctx, curve, n, trusted):
@@ -222,7 +222,7 @@ def test_ragged_msm_vs_oracle(ctx, curve, n, trusted):
 
 # the path switches of a batch call: the one-wave-per-term small path up to 4096 MSM terms (3n + 1
 # for BLS12-381, 4n + 2 for BN254's GLV halves), 13-bit windows from 2^15 + 1 tuples, 16-bit
-# windows and the 2^23-entry accumulation order depth above 2^17 (api.hip run_msm_core, call_wbits)
+# windows and the 2^23-entry accumulation order depth above 2^17 (host_core.hip run_msm_core, call_wbits)
 @pytest.mark.parametrize("curve,n", [("bls12_381", 1365), ("bls12_381", 1366), ("bls12_381", 32768),
                                      ("bls12_381", 32769), ("bls12_381", 131072), ("bls12_381", 131073),
                                      ("bn254", 1023), ("bn254", 1024), ("bn254", 32769)])
@@ -262,7 +262,7 @@ def _context_env(slots, **env):
 
 @pytest.mark.parametrize("curve,log_n", [("bls12_381", 17), ("bls12_381", 20), ("bn254", 17), ("bn254", 20)])
 def test_split_accumulation_vs_oracle(curve, log_n):
-    """The split accumulation (api.hip run_msm_core): MSM#0's bucket sets accumulate in one
+    """The split accumulation (host_core.hip run_msm_core): MSM#0's bucket sets accumulate in one
     launch, then MSM#1's in a second one over the sorted range after them, while MSM#0's
     reduction and window combination run on the slot's side stream.  Forced on
     (KZGMI_SPLIT_ACC=1) and off (=0): A, B and the verdict bit-exact vs the oracle, a corrupted

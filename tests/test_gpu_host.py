@@ -201,14 +201,14 @@ def _context_env(**env):
 @pytest.mark.parametrize("curve,trusted", [("bls12_381", False), ("bls12_381", True), ("bn254", False)])
 def test_sync_host_chunked_matches_unsplit(ctx, curve, trusted):
     """The synchronous host-buffer call splits a large batch into point ranges whose work starts
-    while the next range copies (csrc/api.hip batch_host_chunked): one bucket store for every
+    while the next range copies (csrc/host_batch.hip batch_host_chunked): one bucket store for every
     range (the default without flags or with trusted_g1; BN254 and trusted points take the GLV
     form) and shard partials per range (KZGMI_HOST_CHUNK_MODE=1, the form for the other flags)
     both give the verdict and A, B of a
     context that never splits (KZGMI_HOST_CHUNKS=1) and of the oracle; a corrupted y in the last
     range and in a middle range (second store + merge, then more accumulation) rejects; a
     non-canonical z in an inner range reports the unsplit call's error.  With n = 2^19 + 5000 the
-    ranges are [0, 65536), then three of ~154 K (api.hip enqueue_batch_chunked): index 66536 is
+    ranges are [0, 65536), then three of ~154 K (host_core.hip enqueue_batch_chunked): index 66536 is
     in range 1, n / 2 in range 2."""
     import kzgmi
     import torch

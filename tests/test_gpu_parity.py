@@ -506,7 +506,7 @@ def test_async_slots(ctx, curve, torch_dev):
 
 
 def test_async_accumulation_order(torch_dev):
-    """The accumulation order across slots (api.hip kzgmi_ctx::acc_order, forced on here although 8
+    """The accumulation order across slots (host.hpp kzgmi_ctx::acc_order, forced on here although 8
     slots may share hardware queues): 20 batches of four sizes (both order depths: 2^18 is above
     ACC_ORDER_WIDE) and pipelined MSMs on 8 slots, verdicts and MSM results as submitted, the
     last slots collected out of submission order."""

@@ -42,7 +42,7 @@ out = {"command": "rocprofv3 --kernel-trace --stats -- python3 tools/phase_timin
        **({"k_from29_avg_ms": f29 / 1e6} if f29 else {}),
        "accumulate_phase_avg_ms": (acc + f29 + fix + crowd) / 1e6,
        "accumulate_phase": "k_accumulate + k_fixup + k_fixup_crowded: the kernels between the accumulate "
-                           "phase's two HIP events in csrc/api.hip (bench.py roofline.kernel_ms)"}
+                           "phase's two HIP events in csrc/host.hpp (mark) (bench.py roofline.kernel_ms)"}
 json.dump(out, open(os.path.join(dst, "kernel_single.json"), "w"), indent=1)
 print(json.dumps(out))
 
