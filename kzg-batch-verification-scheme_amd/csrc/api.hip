@@ -296,23 +296,23 @@ int kzgmi_ctx_create_device(kzgmi_ctx** out, int device_id, int pipeline_slots) 
   c->device = device_id;
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && ncu > 0)
-    c->ncu = ncu;
-  if (const char* e = getenv("KZGMI_ACC_THREADS")) c->acc_threads_env = (size_t)strtoull(e, nullptr, 10);
-  if (const char* e = getenv("KZGMI_ACC_QUEUE")) c->acc_queue = atoi(e);
-  if (const char* e = getenv("KZGMI_ACC_QUEUE_MIN")) c->acc_queue_min = std::max<size_t>(4, strtoull(e, nullptr, 10));
-  if (const char* e = getenv("KZGMI_ACC_QUEUE_FROM")) c->acc_queue_from = strtoull(e, nullptr, 10);
-  if (const char* e = getenv("KZGMI_SORT_SPLIT")) c->sort_split = atoi(e) != 0;
-  if (const char* e = getenv("KZGMI_SORT_FULL_BINS")) c->sort_full_bins = atoi(e) != 0;
-  if (const char* e = getenv("KZGMI_WBITS")) c->wbits_env = atoi(e);
-  if (const char* e = getenv("KZGMI_SMALL_TERMS")) c->small_terms = (uint32_t)strtoul(e, nullptr, 10);
+    c->tune.ncu = ncu;
+  if (const char* e = getenv("KZGMI_ACC_THREADS")) c->tune.acc_threads_env = (size_t)strtoull(e, nullptr, 10);
+  if (const char* e = getenv("KZGMI_ACC_QUEUE")) c->tune.acc_queue = atoi(e);
+  if (const char* e = getenv("KZGMI_ACC_QUEUE_MIN")) c->tune.acc_queue_min = std::max<size_t>(4, strtoull(e, nullptr, 10));
+  if (const char* e = getenv("KZGMI_ACC_QUEUE_FROM")) c->tune.acc_queue_from = strtoull(e, nullptr, 10);
+  if (const char* e = getenv("KZGMI_SORT_SPLIT")) c->tune.sort_split = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_SORT_FULL_BINS")) c->tune.sort_full_bins = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_WBITS")) c->tune.wbits_env = atoi(e);
+  if (const char* e = getenv("KZGMI_SMALL_TERMS")) c->tune.small_terms = (uint32_t)strtoul(e, nullptr, 10);
   if (const char* e = getenv("KZGMI_HOST_CHUNKS")) c->host_chunks_env = std::max(1, atoi(e));
   if (const char* e = getenv("KZGMI_HOST_CHUNK_MODE")) c->host_chunk_mode = atoi(e);
-  if (const char* e = getenv("KZGMI_SPLIT_ACC")) c->split_acc = atoi(e) < 0 ? -1 : std::min(1, atoi(e));
-  if (const char* e = getenv("KZGMI_SPLIT_LOWPRIO")) c->split_low_prio = atoi(e) != 0;
-  if (const char* e = getenv("KZGMI_SEG4_WAVES")) c->seg4_waves = std::max(0, atoi(e));
-  if (const char* e = getenv("KZGMI_SPLIT_SIDEFIX")) c->split_side_fix = atoi(e) != 0;
-  if (const char* e = getenv("KZGMI_SPLIT_SIDEPRIO")) c->split_side_prio = atoi(e) != 0;
-  if (const char* e = getenv("KZGMI_SPLIT_REV")) c->split_rev = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_SPLIT_ACC")) c->tune.split_acc = atoi(e) < 0 ? -1 : std::min(1, atoi(e));
+  if (const char* e = getenv("KZGMI_SPLIT_LOWPRIO")) c->tune.split_low_prio = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_SEG4_WAVES")) c->tune.seg4_waves = std::max(0, atoi(e));
+  if (const char* e = getenv("KZGMI_SPLIT_SIDEFIX")) c->tune.split_side_fix = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_SPLIT_SIDEPRIO")) c->tune.split_side_prio = atoi(e) != 0;
+  if (const char* e = getenv("KZGMI_SPLIT_REV")) c->tune.split_rev = atoi(e) != 0;
   if (const char* e = getenv("KZGMI_BLOB_HASH"))
     c->blob_hash = !strcmp(e, "lane") ? BlobLaunch::HASH_LANE : !strcmp(e, "wave") ? BlobLaunch::HASH_WAVE : 0;
   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless set before the runtime
@@ -442,13 +442,8 @@ int kzgmi_ctx_reserve(kzgmi_ctx* c, kzgmi_curve curve, size_t n, uint32_t flags)
   if (n > (1u << 26)) return fail(KZGMI_ERR_ARG, "batch too large (max 2^26 tuples per call)");
   for (auto& s : c->slots)
     if (s.pending) return fail(KZGMI_ERR_ARG, "kzgmi_ctx_reserve with jobs in flight");
-  const Seed none{};
   for (auto& s : c->slots) {
-    if (n)
-      CHK(dispatch(curve, [&](auto cv) -> int {
-        return HostCore<decltype(cv)>::enqueue_batch(c, s, nullptr, nullptr, nullptr, nullptr, nullptr, n, none, 0, nullptr, flags,
-                                                     /*dry=*/true);
-      }));
+    if (n) CHK(dispatch(curve, [&](auto cv) -> int { return HostCore<decltype(cv)>::reserve_batch(c, s, n, flags); }));
     for (auto& e : s.ev)  // the phase events kzgmi_set_profiling records
       if (!e) HIPCHK(hipEventCreate(&e));
   }
@@ -625,7 +620,7 @@ int kzgmi_set_split_acc(kzgmi_ctx* c, int mode) {
   if (mode < -1 || mode > 1) return fail(KZGMI_ERR_ARG, "split mode must be -1, 0 or 1");
   for (auto& s : c->slots)
     if (s.pending) return fail(KZGMI_ERR_ARG, "kzgmi_set_split_acc with jobs in flight");
-  c->split_acc = mode;
+  c->tune.split_acc = mode;
   for (kzgmi_ctx* p : c->peers) CHK(kzgmi_set_split_acc(p, mode));
   return set_dev(c);
 }

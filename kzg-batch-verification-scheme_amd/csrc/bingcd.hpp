@@ -133,8 +133,8 @@ struct BinGcd {
     const int steps = (2 * len_m - 1 + K - 1) / K;
     for (int it = 0; it < steps; ++it) {
       const int la = bitlen(a), lb = bitlen(b);
-      // a = 0: b = gcd = 1 and every further step keeps v (f0 = 1, g0 = 0, f1 = g1 = 2^K:
-      // u <- u / 2^K, v <- v).  Random 381-bit inputs get there after 17-20 of the 26 steps
+      // a = 0: b = gcd = 1 and every further step only shifts a, so it keeps b and v (f0 = 1,
+      // g0 = 0, f1 = 0, g1 = 2^K: u <- u / 2^K, v <- v, b <- b).  Random 381-bit inputs get there after 17-20 of the 26 steps
       // (variable time: a verifier's inputs are public)
       if (la == 0) break;
       int n = la > lb ? la : lb;

@@ -5,6 +5,7 @@
 // the copy pool) is defined exactly once, in api.hip, and only declared here.
 #pragma once
 #include "launch.hpp"
+#include "msm_plan.hpp"
 #include "kzgmi.h"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -106,9 +107,9 @@ struct Slot {
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
   DevBuf acc29b, cntb, offb;                     // second bucket store of chunked batches (run_msm_core part)
-  // split accumulation (run_msm_core): the second MSM's reduction and window combination run on
-  // the context's side stream beside the first MSM's accumulation; side_ev[0] = its sets
-  // accumulated, [1] = combined
+  // split accumulation (run_msm_core): the MSM of the first accumulation launch (MSM#0 by default,
+  // MsmTuning::split_rev) reduces and combines on the context's one side stream beside the second
+  // launch; side_ev[0] = the first launch's sets accumulated, [1] = its MSM combined
   hipEvent_t side_ev[2] = {};
   int* host_flags = nullptr;  // pinned: [ok, err]
   uint8_t* host_out = nullptr;  // pinned: encoded MSM result of an async MSM job
@@ -153,42 +154,13 @@ struct kzgmi_ctx {
   bool glv_msm = true;      // enable knobs (kzgmi_set_glv; A/B measurements)
   bool glv_batch = true;
   bool msm_trusted_g1 = false;
-  // accumulation grid cap: one resident round (CUs x 4 SIMDs x kAccWaves<Cv> waves x 64 lanes)
-  // of equal chunks instead of 64-entry chunks in 2-3 partial rounds: 113 -> 116
-  // batch-verifies/s pipelined when introduced (tools/ab.py).
-  int ncu = 0;                // compute units: the accumulation grid cap (kAccWaves, msm.hpp)
-  size_t acc_threads_env = 0;  // KZGMI_ACC_THREADS override of that cap (0 = none)
-  int acc_queue = ACC_QUEUE_FACTOR;  // KZGMI_ACC_QUEUE: chunks per capped thread (<= 1: static grid)
-  size_t acc_queue_min = ACC_QUEUE_MIN_LEN;  // KZGMI_ACC_QUEUE_MIN: shortest queue chunk (entries)
-  size_t acc_queue_from = ACC_QUEUE_FROM;    // KZGMI_ACC_QUEUE_FROM: calls with fewer entries keep the static grid
-  bool sort_split = false;     // KZGMI_SORT_SPLIT: split coarse-pass entries at every size (tests)
-  bool sort_full_bins = false;  // KZGMI_SORT_FULL_BINS: the set-table-overflow fallback at every size (tests)
-  int wbits_env = 0;           // KZGMI_WBITS: 13 or 16 forces the window width (tests, A/B)
-  uint32_t small_terms = 4096;  // calls of at most this many terms: msm_small.hpp (KZGMI_SMALL_TERMS; 0: never)
+  MsmTuning tune;  // what plan_msm decides an MSM call by (msm_plan.hpp): the device's CUs and the KZGMI_* knobs
   int host_chunks_env = 0;       // KZGMI_HOST_CHUNKS: ranges of a synchronous host-buffer batch (batch_host_chunked)
   int host_chunk_mode = 0;       // KZGMI_HOST_CHUNK_MODE=1: shard partials even where one bucket store applies
-  // Split accumulation of two-MSM calls (run_msm_core): -1 synchronous device calls of at least
-  // SPLIT_FROM entries with no other slot in flight (latency-bound), 0 never, 1 always
-  // (KZGMI_SPLIT_ACC).  Single 2^20 BLS12-381 batches 8.02 -> 7.95 ms; 2^17 ones lose (2.95 ->
-  // 3.01 ms: the side work outlasts the short second launch), so smaller calls keep one launch
-  // (profiles/r06/split_accumulation.txt, ab_split_rev.txt)
-  static constexpr size_t SPLIT_FROM = size_t(1) << 25;
-  int split_acc = -1;
-  bool split_low_prio = true;    // KZGMI_SPLIT_LOWPRIO: the side stream's kernels without the tail's raised issue priority
-  bool split_side_fix = true;    // KZGMI_SPLIT_SIDEFIX: the first launch's piece joins on the side stream
-  bool split_side_prio = true;   // KZGMI_SPLIT_SIDEPRIO: the side stream at the device's greatest priority
-  // KZGMI_SPLIT_REV: MSM#0's sets (8 windows) in the first launch, its short tail on the side
-  // stream, hidden behind MSM#1's 3x longer launch; MSM#1's tail after it on an idle chip.  0:
-  // MSM#1's first, whose side tail outlasts the short second launch.  2^20: 7.95 vs 7.98 ms
-  // (one launch 8.02; profiles/r06/ab_split_rev.txt)
-  bool split_rev = true;
   // set by the synchronous device-buffer call while it enqueues: only such calls split (the first
   // batch of a pipeline is alone when it is enqueued too, and split it cost the 20-step bench
   // ~1 ms: its two launches, then a gap while the next batch's front end ran)
   bool sync_call = false;
-  // reduction segments on 4 threads instead of 2 while that grid stays within seg4_waves waves per
-  // SIMD (Launch::reduce; KZGMI_SEG4_WAVES, 0: always 2)
-  int seg4_waves = 1;
   // accumulation order: a slot's k_accumulate waits for the accumulation D launches before it
   // (any slot), so at most D run at once and they start in submission order.  Without it 16
   // slots in flight ran their accumulations in bursts and their tails (pairing: one CU) together,
@@ -484,14 +456,14 @@ template <class Cv>
 struct HostCore {
   static int run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uint32_t nsets, size_t emax,
                           const MsmWindows& mw, const Affine<Cv>* pts = nullptr, const uint8_t* inf = nullptr,
-                          bool pts29 = false, bool dry = false, int wbits = WBITS, int part = 0);
+                          bool pts29 = false, int wbits = WBITS, int part = 0);
   static int enqueue_fs_digests(Slot& s, const void* dC, const void* dpi, const void* dz, const void* dy, size_t n,
                                 uint64_t offset, bool compressed, const uint32_t** digests_out);
   static int enqueue_fs_challenge(Slot& s, const uint32_t* digests, uint32_t nch, uint64_t n_total);
   static int enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, const void* dz, const void* dy,
                            const void* dpi, size_t n, const Seed& seed, uint64_t offset, void* d_partial_out,
-                           uint32_t flags, bool dry = false, const void* d_blobs = nullptr,
-                           const CellJob* cell = nullptr);
+                           uint32_t flags, const void* d_blobs = nullptr, const CellJob* cell = nullptr);
+  static int reserve_batch(kzgmi_ctx* c, Slot& s, size_t n, uint32_t flags);
   static int enqueue_batch_chunked(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const uint8_t* hC, const uint8_t* hz,
                                    const uint8_t* hy, const uint8_t* hpi, size_t n, const Seed& seed, uint32_t flags,
                                    int k);

@@ -5,52 +5,63 @@
 
 namespace kzgmi {
 
-// ------------------------------------------------------------------------------ small MSMs
-// The terms of tl (classes in order) as one wave each, MSM m's leaves in class order; the tree's
-// stored nodes and arrival counters per MSM, level after level (msm_small.hpp).
+// ------------------------------------------------------------------------------ MSM core
+// Every MSM call is planned as plain data (msm_plan.hpp plan_msm), then the slot's buffers grow to
+// the plan's sizes (ensure_msm), then the plan is enqueued.
+
+// no other slot of the context has a job in flight (such a call is latency-bound)
+static bool slot_alone(const kzgmi_ctx* c, const Slot& s) {
+  bool alone = true;
+  for (const Slot& o : c->slots) alone &= &o == &s || !o.pending;
+  return alone;
+}
+
+// the slot's buffers at the sizes plan p asks for; a refused plan fails here
+static int ensure_msm(Slot& s, const MsmPlan& p) {
+  if (p.refuse) return fail(KZGMI_ERR_ARG, p.refuse);
+  const MsmBytes& z = p.bytes;
+  if (p.small) {
+    CHK(s.small_nodes.ensure(z.small_nodes));
+    CHK(s.small_flags.ensure(z.small_flags));
+    return s.res.ensure(z.res);
+  }
+  CHK(s.digits.ensure(z.digits));
+  CHK(s.cnt.ensure(z.cnt));
+  CHK(s.off.ensure(z.off));
+  if (p.second) {
+    CHK(s.cntb.ensure(z.cntb));
+    CHK(s.offb.ensure(z.offb));
+  }
+  CHK(s.coarse.ensure(z.coarse));
+  CHK(s.ent.ensure(z.ent));
+  CHK(s.total.ensure(z.total));
+  if (p.acc_threads) CHK(s.accq.ensure(z.accq));
+  CHK(s.crowd.ensure(z.crowd));
+  CHK(s.sval.ensure(z.sval));
+  CHK(s.skey.ensure(z.skey));
+  CHK(s.acc29.ensure(z.acc29));
+  if (p.second) CHK(s.acc29b.ensure(z.acc29b));
+  CHK(s.R.ensure(z.R));
+  CHK(s.U.ensure(z.U));
+  CHK(s.scratch.ensure(z.scratch));
+  CHK(s.winsum.ensure(z.winsum));
+  if (z.small_nodes) {  // plan_reserve: the tree of a smaller call in the small form
+    CHK(s.small_nodes.ensure(z.small_nodes));
+    CHK(s.small_flags.ensure(z.small_flags));
+  }
+  return s.res.ensure(z.res);
+}
+
+// small calls: one wave per term and a summation tree (msm_small.hpp) instead of buckets
 template <class Cv>
-static int run_small_msm(kzgmi_ctx* c, Slot& s, const TermList& tl, const MsmWindows& mw, const Affine<Cv>* pts,
-                  const uint8_t* inf, bool own_pts, bool dry) {
-  SmallPlan sp{};
-  sp.nclass = tl.nclass;
-  sp.nmsm = mw.nmsm;
-  uint32_t terms = 0, leaves[2] = {0, 0};
-  for (uint32_t k = 0; k < tl.nclass; ++k) {
-    const uint32_t m = mw.nmsm > 1 && tl.c[k].set_base >= mw.set_base[1] ? 1 : 0;
-    sp.term_base[k] = terms;
-    sp.msm[k] = m;
-    sp.leaf_base[k] = leaves[m];
-    terms += tl.c[k].count;
-    leaves[m] += tl.c[k].count;
-  }
-  uint32_t nodes = 0, flags = 0;
-  for (uint32_t m = 0; m < 2; ++m) {
-    sp.count[m] = leaves[m];
-    sp.node_base[m] = nodes;
-    sp.flag_base[m] = flags;
-    for (uint32_t cnt = leaves[m]; cnt > 1; cnt = (cnt + 1) >> 1) {
-      nodes += cnt;
-      flags += (cnt + 1) >> 1;
-    }
-  }
-  CHK(s.small_nodes.ensure((size_t)(nodes + 1) * SMALL_NODE_WORDS * 4));
-  CHK(s.small_flags.ensure((size_t)(flags + 1) * 4));
-  CHK(s.res.ensure(2 * sizeof(Xyzz<Cv>)));
-  if (dry) return 0;
+static int enqueue_small_msm(kzgmi_ctx* c, Slot& s, const MsmPlan& p, const Affine<Cv>* pts, const uint8_t* inf) {
   Roctx rx("kzgmi.msm.small");
   hipStream_t st = s.stream;
   using L = Launch<Cv>;
-  if (!pts) pts = s.pts.template as<Affine<Cv>>();
-  if (!inf) inf = s.inf.template as<uint8_t>();
-  if (own_pts) {  // the slot's points into the radix-29 slots the kernel reads
-    uint32_t npts = 0;
-    for (uint32_t k = 0; k < tl.nclass; ++k)
-      if (tl.c[k].count) npts = std::max(npts, tl.c[k].pt_base + tl.c[k].count);
-    L::pts_to29(st, s.pts.template as<Affine<Cv>>(), npts);
-  }
+  L::pts_to29(st, s.pts.template as<Affine<Cv>>(), p.own_npts);  // into the radix-29 slots the kernel reads
   mark(c, s, PH_SORT + 1);
-  L::small_msm(st, tl, sp, terms, pts, inf, s.small_nodes.template as<uint32_t>(), s.small_flags.template as<uint32_t>(),
-               flags + 1, s.res.template as<Xyzz<Cv>>());
+  L::small_msm(st, p.tl, p.sp, p.small_terms, pts, inf, s.small_nodes.template as<uint32_t>(),
+               s.small_flags.template as<uint32_t>(), p.small_flags + 1, s.res.template as<Xyzz<Cv>>());
   mark(c, s, PH_ACCUM + 1);
   mark(c, s, PH_REDUCE + 1);
   mark(c, s, PH_COMBINE + 1);
@@ -58,132 +69,53 @@ static int run_small_msm(kzgmi_ctx* c, Slot& s, const TermList& tl, const MsmWin
   return 0;
 }
 
-// ------------------------------------------------------------------------------ MSM core
-// part (chunked host-buffer batches, enqueue_batch_chunked): 0 the whole call; 1 the first point
-// range -- sort + accumulate into the slot's bucket store, no reduction; 2 a middle range -- into
-// the second store (acc29b, cntb, offb), merged into the first; 3 the last range -- as 2, then the
-// reduction and window combination of the merged store
+// part: the range of a chunked host-buffer batch this call is (msm_plan.hpp plan_msm)
 template <class Cv>
 int HostCore<Cv>::run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uint32_t nsets, size_t emax, const MsmWindows& mw,
-                 const Affine<Cv>* pts, const uint8_t* inf, bool pts29, bool dry, int wbits, int part) {
-  const uint32_t nbuckets = wbits == 13 ? Win<13>::NBUCKETS : Win<WBITS>::NBUCKETS;
-  const uint32_t bins = wbits == 13 ? Win<13>::BINS : Win<WBITS>::BINS;
-  const uint32_t rb_parts = wbits == 13 ? Win<13>::RB_PARTS : Win<WBITS>::RB_PARTS;
+                 const Affine<Cv>* pts, const uint8_t* inf, bool pts29, int wbits, int part) {
   // pts == nullptr: the slot's freshly converted points, put into the accumulation's format
   // here unless convert_points stored them in it already (pts29); explicit pts (commit-key
   // rows) are stored in that format already (kzgmi_ck_load)
   const bool own_pts = pts == nullptr && !pts29;
-  // small calls: one wave per term and a summation tree (msm_small.hpp) instead of buckets
-  {
-    bool small = part == 0 && c->small_terms && tl_in.total <= c->small_terms && mw.nmsm <= 2;
-    for (uint32_t k = 0; k < tl_in.nclass; ++k) small = small && tl_in.c[k].win_off == 0;
-    if (small) return run_small_msm<Cv>(c, s, tl_in, mw, pts, inf, own_pts, dry);
-  }
-  TermList tl = tl_in;  // + each class's offset in the digit array
-  size_t ndig = 0;
-  for (uint32_t k = 0; k < tl.nclass; ++k) {
-    tl.c[k].dig_base = (uint32_t)ndig;
-    ndig += (size_t)tl.c[k].count * tl.c[k].nwin;
-  }
-  if (ndig >= (1ull << 32)) return fail(KZGMI_ERR_ARG, "too many window digits for one call");
-  CHK(s.digits.ensure(ndig * 4));
+  const MsmTuning& t = c->tune;
+  const MsmPlan p = plan_msm<Cv>(t, tl_in, nsets, emax, mw, wbits, part, own_pts, slot_alone(c, s), c->sync_call);
+  CHK(ensure_msm(s, p));
   using XY = Xyzz<Cv>;
+  using L = Launch<Cv>;
   if (!pts) pts = s.pts.template as<Affine<Cv>>();  // default: the slot's converted points
   if (!inf) inf = s.inf.template as<uint8_t>();
-  const uint32_t NB = nsets * nbuckets;
-  // accumulation threads: 64-entry chunks (16 for small calls, msm.hpp ACC_CHUNK_SMALL), at most
-  // one resident round of them (then equal longer chunks)
-  const size_t chunk = emax <= ACC_SMALL_ENTRIES ? ACC_CHUNK_SMALL : ACC_CHUNK;
-  size_t nchunks = (emax + chunk - 1) / chunk + 1;
-  const size_t cap = c->acc_threads_env ? c->acc_threads_env : (size_t)c->ncu * 4 * kAccWaves<Cv> * 64;
-  if (cap && nchunks > cap) nchunks = cap;
-  // A call with no other slot of the context in flight is latency-bound: below the cap, give
-  // every SIMD the same whole number of waves (shorter equal chunks).  A 2^17 batch at 13 bits
-  // is 1.25 waves per SIMD, and its SIMDs with two waves ran 1.5x longer than those with one:
-  // 4.36 -> 3.99 ms per batch.  Pipelined calls keep the longer chunks (fewer pieces to join:
-  // 2^17 batches 1014 vs 966/s with the rounding; profiles/r03/misc_ab_r03.txt).
-  // (kzgmi_ctx_reserve sizes the piece arrays for the rounded count)
-  bool alone = true;
-  for (const Slot& o : c->slots) alone &= &o == &s || !o.pending;
-  alone |= dry;
-  const size_t simd_lanes = (size_t)c->ncu * 4 * 64;
-  if (alone && !c->acc_threads_env && emax > ACC_SMALL_ENTRIES && simd_lanes && nchunks < cap)
-    nchunks = std::min(cap, (nchunks + simd_lanes - 1) / simd_lanes * simd_lanes);
-  // Large radix-29 calls (the grid at its cap): c->acc_queue x cap shorter chunks taken from a
-  // work queue by the cap's threads (msm.hpp k_accumulate), so an accumulation that starts behind
-  // another slot's still ends on every CU at about the same time.  The part arrays and k_fixup
-  // are sized for the chunk count.
-  size_t acc_threads = 0;
-  if (c->acc_queue > 1 && cap && nchunks == cap && cap % 256 == 0 && emax >= c->acc_queue_from) {
-    acc_threads = cap;
-    nchunks = std::min(cap * (size_t)c->acc_queue, std::max(cap, emax / c->acc_queue_min));
-    if (nchunks <= cap) acc_threads = 0;
-  }
-  nchunks = (nchunks + 255) / 256 * 256;  // = the launched thread count (part arrays indexed by thread)
-  // Split accumulation (latency): the two MSMs' sets (MSM#1's a suffix of the sets) accumulate
-  // in two launches; the first launch's MSM reduces and combines on the slot's side stream beside
-  // the second launch (split_rev: which MSM goes first).
-  const uint32_t split_set = mw.nmsm == 2 ? mw.set_base[1] : 0;
-  const bool can_split = part == 0 && mw.set_base[0] == 0 && split_set > 0 && split_set + mw.nwin[1] == nsets &&
-                         mw.nwin[0] == split_set && c->split_acc != 0;
-  // auto: only where the second MSM's tail is the longer one (BLS12-381 without GLV: 16 windows
-  // against 8).  GLV batches (BN254, trusted BLS12-381 points) have 8 windows in both MSMs: the
-  // split only adds its side-stream contention (BN254 2^22: 14.70 -> 15.18 ms)
-  const bool split = can_split && (c->split_acc > 0 || (alone && c->sync_call && emax >= kzgmi_ctx::SPLIT_FROM &&
-                                                        mw.nwin[1] > mw.nwin[0]));
-  const size_t nchunks_b = nchunks, acc_threads_b = acc_threads;  // the second launch's grid
-  // pieces: [A's first | A's last | B's first | B's last] when A's joins run on the side stream
-  const size_t pieces = can_split && c->split_side_fix ? nchunks + nchunks_b : std::max(nchunks, nchunks_b);
-  const size_t crowd_words = 1 + 3 * (pieces / FIX_LP_FROM + 2);  // at most one per FIX_LP_FROM + 1 chunks
-  CHK(s.cnt.ensure((size_t)NB * 4));
-  CHK(s.off.ensure((size_t)NB * 4));
-  const bool second = part >= 2;  // this range accumulates into the second store, then merges
-  if (second) {
-    CHK(s.cntb.ensure((size_t)NB * 4));
-    CHK(s.offb.ensure((size_t)NB * 4));
-  }
-  DevBuf& CNT = second ? s.cntb : s.cnt;
-  DevBuf& OFF = second ? s.offb : s.off;
-  DevBuf& ACC = second ? s.acc29b : s.acc29;
-  CHK(s.coarse.ensure((size_t)3 * nsets * bins * 4));
-  CHK(s.ent.ensure(emax * 8));
-  CHK(s.total.ensure(16));
-  if (acc_threads || acc_threads_b) CHK(s.accq.ensure(16));
-  CHK(s.crowd.ensure(4 * crowd_words * (can_split ? 2 : 1)));  // a split's second list after the first
-  CHK(s.sval.ensure(emax * 4 + 16));  // + 16: k_accumulate reads values 4 at a time, up to 3 past the end
-  CHK(s.skey.ensure(emax * 4));
-  constexpr int W29 = kW29<Fp29Of<Cv>>;
-  // buckets and bucket pieces are radix-29 records in acc29 (msm.hpp)
-  CHK(s.acc29.ensure(((size_t)NB + 2 * pieces) * W29 * 4));
-  if (second) CHK(s.acc29b.ensure(((size_t)NB + 2 * nchunks) * W29 * 4));
-  const size_t seg_rec = (size_t)W29 * 4;  // a radix-29 record
-  CHK(s.R.ensure((size_t)NB / SEG * seg_rec));
-  CHK(s.U.ensure((size_t)NB / SEG * seg_rec * 2));  // U records, then the V records
-  CHK(s.scratch.ensure((size_t)nsets * rb_parts * sizeof(XY)));  // k_reduce_bits partial sums
-  CHK(s.winsum.ensure((size_t)nsets * sizeof(XY)));
-  CHK(s.res.ensure(2 * sizeof(XY)));
-  if (dry) return 0;  // kzgmi_ctx_reserve: workspace sized, nothing enqueued
-  if (split && !c->side_stream) {  // at the slot stream's priority, or the device's greatest
+  if (p.small) return enqueue_small_msm<Cv>(c, s, p, pts, inf);
+  const TermList& tl = p.tl;
+  const uint32_t NB = p.NB, nbuckets = p.nbuckets;
+  const size_t nchunks = p.nchunks, acc_threads = p.acc_threads;
+  uint32_t* const coarse = s.coarse.template as<uint32_t>();
+  uint32_t* const total = s.total.template as<uint32_t>();
+  uint32_t* const sval = s.sval.template as<uint32_t>();
+  uint32_t* const skey = s.skey.template as<uint32_t>();
+  uint32_t* const cnt = s.cnt.template as<uint32_t>();
+  uint32_t* const off = s.off.template as<uint32_t>();
+  uint32_t* const acc = s.acc29.template as<uint32_t>();  // buckets and bucket pieces: radix-29 records (msm.hpp)
+  uint32_t* const accq = acc_threads ? s.accq.template as<uint32_t>() : nullptr;
+  uint32_t* const crowd = s.crowd.template as<uint32_t>();
+  XY* const scratch = s.scratch.template as<XY>();
+  XY* const winsum = s.winsum.template as<XY>();
+  XY* const res = s.res.template as<XY>();
+  if (p.split && !c->side_stream) {  // at the slot stream's priority, or the device's greatest
     int prio = 0, least = 0, greatest = 0;
     HIPCHK(hipStreamGetPriority(s.stream, &prio));
-    if (c->split_side_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) prio = greatest;
+    if (t.split_side_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) prio = greatest;
     HIPCHK(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, prio));
   }
-  if (split && !s.side_ev[0])
+  if (p.split && !s.side_ev[0])
     for (auto& e : s.side_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   Roctx rx("kzgmi.msm.sort+accumulate+reduce+combine");
   hipStream_t st = s.stream;
-  using L = Launch<Cv>;
-  if (own_pts) {
-    uint32_t npts = 0;
-    for (uint32_t k = 0; k < tl.nclass; ++k)
-      if (tl.c[k].count) npts = std::max(npts, tl.c[k].pt_base + tl.c[k].count);
-    L::pts_to29(st, s.pts.template as<Affine<Cv>>(), npts);
-  }
-  L::sort(st, tl, nsets, inf, s.digits.template as<uint32_t>(), s.coarse.template as<uint32_t>(), s.ent.template as<uint64_t>(), emax,
-          (c->sort_split ? L::SORT_SPLIT : 0) | (c->sort_full_bins ? L::SORT_FULL_BINS : 0),
-          OFF.template as<uint32_t>(), CNT.template as<uint32_t>(), s.total.template as<uint32_t>(),
-          s.sval.template as<uint32_t>(), s.skey.template as<uint32_t>(), wbits);
+  L::pts_to29(st, s.pts.template as<Affine<Cv>>(), p.own_npts);
+  // a range of parts 2 and 3 sorts and accumulates into the second store
+  L::sort(st, tl, nsets, inf, s.digits.template as<uint32_t>(), coarse, s.ent.template as<uint64_t>(), emax,
+          (t.sort_split ? L::SORT_SPLIT : 0) | (t.sort_full_bins ? L::SORT_FULL_BINS : 0),
+          p.second ? s.offb.template as<uint32_t>() : off, p.second ? s.cntb.template as<uint32_t>() : cnt, total, sval, skey,
+          wbits);
   mark(c, s, PH_SORT + 1);
   hipEvent_t* order_ev = nullptr;  // accumulation order (kzgmi_ctx::acc_order)
   const int order = emax >= kzgmi_ctx::ACC_ORDER_WIDE ? c->acc_order : c->acc_order_small;
@@ -195,53 +127,46 @@ int HostCore<Cv>::run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uin
     order_ev = &c->acc_ring[i % M];  // (launch i - M's event: no later launch waits for it)
     if (!*order_ev) HIPCHK(hipEventCreateWithFlags(order_ev, hipEventDisableTiming));
   }
-  if (split) {
+  if (p.split) {
+    // Two launches A and B of the same grid, one per MSM: A's MSM reduces and combines on the
+    // context's side stream while B accumulates on the slot's.
     // sets [split_set, nsets) are the sorted entries [coff[split_set * bins], total)
-    const uint32_t* mid = s.coarse.template as<uint32_t>() + (size_t)nsets * bins + (size_t)split_set * bins;
-    const uint32_t h = split_set, hn = nsets - split_set;
-    uint32_t* acc = s.acc29.template as<uint32_t>();
-    uint32_t* crowd_a = s.crowd.template as<uint32_t>();
-    uint32_t* crowd_b = crowd_a + crowd_words;
+    const uint32_t* mid = coarse + (size_t)nsets * p.bins + (size_t)p.split_set * p.bins;
+    const uint32_t h = p.split_set, hn = nsets - p.split_set;
+    uint32_t* crowd_b = crowd + p.crowd_words;
     // launch A's pieces follow the buckets, launch B's follow A's: A's joins may run on the side
-    // stream while B accumulates.  Order: MSM#1's sets [mid, total) first (split_rev 0), or
-    // MSM#0's [0, mid) first (1); the first launch's MSM finishes on the side stream.
-    const bool rev = c->split_rev;
-    const uint32_t* total_a = rev ? mid : s.total.template as<uint32_t>();
+    // stream while B accumulates.  Order: MSM#0's sets [0, mid) first (split_rev 1, the default),
+    // or MSM#1's [mid, total) first (0); the first launch's MSM finishes on the side stream.
+    const bool rev = t.split_rev;
+    const uint32_t* total_a = rev ? mid : total;
     const uint32_t* lo_a = rev ? nullptr : mid;
-    const uint32_t* total_b = rev ? s.total.template as<uint32_t>() : mid;
+    const uint32_t* total_b = rev ? total : mid;
     const uint32_t* lo_b = rev ? mid : nullptr;
-    const uint32_t nb_b = c->split_side_fix ? (uint32_t)(NB + 2 * nchunks) : NB;
-    L::accumulate(st, nchunks, total_a, s.sval.template as<uint32_t>(), s.skey.template as<uint32_t>(),
-                  s.off.template as<uint32_t>(), s.cnt.template as<uint32_t>(), pts, acc, NB, acc_threads,
-                  acc_threads ? s.accq.template as<uint32_t>() : nullptr, crowd_a, lo_a,
-                  c->split_side_fix ? nullptr : st);
+    const uint32_t nb_b = t.split_side_fix ? (uint32_t)(NB + 2 * nchunks) : NB;
+    L::accumulate(st, nchunks, total_a, sval, skey, off, cnt, pts, acc, NB, acc_threads, accq, crowd, lo_a,
+                  t.split_side_fix ? nullptr : st);
     hipStream_t sd = c->side_stream;
     HIPCHK(hipEventRecord(s.side_ev[0], st));
     HIPCHK(hipStreamWaitEvent(sd, s.side_ev[0], 0));
-    L::accumulate(st, nchunks_b, total_b, s.sval.template as<uint32_t>(), s.skey.template as<uint32_t>(),
-                  s.off.template as<uint32_t>(), s.cnt.template as<uint32_t>(), pts, acc, nb_b, acc_threads_b,
-                  acc_threads_b ? s.accq.template as<uint32_t>() : nullptr, crowd_b, lo_b, st);
+    L::accumulate(st, nchunks, total_b, sval, skey, off, cnt, pts, acc, nb_b, acc_threads, accq, crowd_b, lo_b, st);
     if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));
     // MSM m's reduction and window combination on stream q: bucket records, R / U+V records, bit
     // sums and window sums at the offsets of its sets
+    constexpr int W29 = kW29<Fp29Of<Cv>>;
     const size_t nseg = nbuckets / SEG;
     uint32_t* R29 = s.R.template as<uint32_t>();
     uint32_t* U29 = s.U.template as<uint32_t>();
     auto tail = [&](hipStream_t q, int m, bool lowp) {
       const uint32_t s0 = m ? h : 0, ns = m ? hn : h;
-      L::reduce(q, ns, s.cnt.template as<uint32_t>() + (size_t)s0 * nbuckets, acc + (size_t)s0 * nbuckets * W29,
+      L::reduce(q, ns, cnt + (size_t)s0 * nbuckets, acc + (size_t)s0 * nbuckets * W29,
                 reinterpret_cast<XY*>(R29 + s0 * nseg * W29), reinterpret_cast<XY*>(U29 + 2 * s0 * nseg * W29),
-                s.scratch.template as<XY>() + (size_t)s0 * rb_parts, s.winsum.template as<XY>() + s0, wbits, lowp,
-                c->seg4_waves, 4 * c->ncu);
+                scratch + (size_t)s0 * p.rb_parts, winsum + s0, wbits, lowp, t.seg4_waves, 4 * t.ncu);
       if (q == st) mark(c, s, PH_REDUCE + 1);
-      L::window_combine(q, MsmWindows{1, {s0, 0}, {mw.nwin[m], 0}}, s.winsum.template as<XY>(),
-                        s.res.template as<XY>() + m, wbits, lowp);
+      L::window_combine(q, MsmWindows{1, {s0, 0}, {mw.nwin[m], 0}}, winsum, res + m, wbits, lowp);
     };
     // side: (A's piece joins,) the first launch's MSM
-    if (c->split_side_fix)
-      L::fixup(sd, nchunks, total_a, s.skey.template as<uint32_t>(), s.off.template as<uint32_t>(),
-               s.cnt.template as<uint32_t>(), acc, NB, crowd_a, lo_a);
-    tail(sd, rev ? 0 : 1, c->split_low_prio);
+    if (t.split_side_fix) L::fixup(sd, nchunks, total_a, skey, off, cnt, acc, NB, crowd, lo_a);
+    tail(sd, rev ? 0 : 1, t.split_low_prio);
     HIPCHK(hipEventRecord(s.side_ev[1], sd));
     mark(c, s, PH_ACCUM + 1);
     tail(st, rev ? 1 : 0, false);
@@ -250,24 +175,26 @@ int HostCore<Cv>::run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uin
     HIPCHK(hipGetLastError());
     return 0;
   }
-  L::accumulate(st, nchunks, s.total.template as<uint32_t>(), s.sval.template as<uint32_t>(), s.skey.template as<uint32_t>(),
-                OFF.template as<uint32_t>(), CNT.template as<uint32_t>(), pts, ACC.template as<uint32_t>(), NB,
-                acc_threads, acc_threads ? s.accq.template as<uint32_t>() : nullptr, s.crowd.template as<uint32_t>(),
-                nullptr, st);
-  if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));
-  if (second)
-    L::merge_buckets(st, NB, s.acc29.template as<uint32_t>(), s.cnt.template as<uint32_t>(),
-                     s.acc29b.template as<uint32_t>(), s.cntb.template as<uint32_t>());
+  if (p.second) {
+    uint32_t* const accb = s.acc29b.template as<uint32_t>();
+    uint32_t* const cntb = s.cntb.template as<uint32_t>();
+    L::accumulate(st, nchunks, total, sval, skey, s.offb.template as<uint32_t>(), cntb, pts, accb, NB, acc_threads, accq,
+                  crowd, nullptr, st);
+    if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));
+    L::merge_buckets(st, NB, acc, cnt, accb, cntb);
+  } else {
+    L::accumulate(st, nchunks, total, sval, skey, off, cnt, pts, acc, NB, acc_threads, accq, crowd, nullptr, st);
+    if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));
+  }
   mark(c, s, PH_ACCUM + 1);
   if (part == 1 || part == 2) {
     HIPCHK(hipGetLastError());
     return 0;  // more ranges follow
   }
-  L::reduce(st, nsets, s.cnt.template as<uint32_t>(), s.acc29.template as<uint32_t>(), s.R.template as<XY>(),
-            s.U.template as<XY>(), s.scratch.template as<XY>(), s.winsum.template as<XY>(), wbits, false, c->seg4_waves,
-            4 * c->ncu);
+  L::reduce(st, nsets, cnt, acc, s.R.template as<XY>(), s.U.template as<XY>(), scratch, winsum, wbits, false,
+            t.seg4_waves, 4 * t.ncu);
   mark(c, s, PH_REDUCE + 1);
-  L::window_combine(st, mw, s.winsum.template as<XY>(), s.res.template as<XY>(), wbits);
+  L::window_combine(st, mw, winsum, res, wbits);
   mark(c, s, PH_COMBINE + 1);
   HIPCHK(hipGetLastError());
   return 0;
@@ -326,74 +253,104 @@ static int reserve_fs(Slot& s, size_t n) {
   return 0;
 }
 
-// Window width of a call from its entry count at c = 16 (msm.hpp Win): c = 13 for mid-size calls,
-// 2^20 < entries <= max13 (batches: 2^15 < n <= 2^17, max13 = 2^22; MSMs: 2^16 < n <= 2^17,
-// max13 = 2^21) -- 8x fewer buckets for 5/4 the terms, where the bucket-sum reduction is a large
-// share of the pipelined work (2^17-tuple batches 875 -> 1024/s, 2^17-point MSMs 193 -> 224 M
-// pts/s; profiles/r03/misc_ab_r03.txt).  Not for larger calls (a 2^18-point MSM: 270 -> 242)
-// nor tiny ones, whose latency it raises: the top window of a 10 x 13-bit split of a 128-bit
-// magnitude holds 11 bits (of a 20 x 13 split of 256 bits, 9), so its terms crowd into a few
-// hundred buckets whose pieces k_fixup joins serially (n = 256: 3.0 -> 3.3 ms).  At 14 bits the
-// top windows keep 2 and 4 bits: a 2^17 batch took 19 ms.  KZGMI_WBITS=13/16 forces one.
-static int call_wbits(const kzgmi_ctx* c, size_t entries16, size_t max13) {
-  if (c->wbits_env == 13 || c->wbits_env == WBITS) return c->wbits_env;
-  return entries16 > (size_t(1) << 20) && entries16 <= max13 ? 13 : WBITS;
-}
-// windows of a 127-bit magnitude (randomisers, GLV halves) and of a full 255-bit scalar at width c
-// (signed digits: the top window takes the last carry)
-inline uint32_t windows_half(int wb) { return (uint32_t)((128 + wb - 1) / wb); }
-inline uint32_t windows_full(int wb) { return (uint32_t)((256 + wb - 1) / wb); }
-
 // ------------------------------------------------------------------------------ batch
-template <class Cv>
-int HostCore<Cv>::enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, const void* dz, const void* dy,
-                  const void* dpi, size_t n, const Seed& seed, uint64_t offset, void* d_partial_out,
-                  uint32_t flags, bool dry, const void* d_blobs, const CellJob* cell) {
-  using XY = Xyzz<Cv>;
-  using FrF = Fp<typename Cv::FrP>;
-  const bool glv = c->glv_batch &&
-                   (Cv::ID == 1 || (flags & (KZGMI_FLAG_SUBGROUP_CHECK | KZGMI_FLAG_TRUSTED_G1)) != 0);
-  // MSM#1's tail class: -t [1]_1, or for a cell batch (BLS12-381, powers + compressed + subgroup
-  // check) the 64 terms -c_m [tau^m]_1
-  const uint32_t tail = cell ? CellLaunch::TERMS : 1;
-  // points: [pi (n) | C (n) | tail]; a cell batch keeps its m decoded unique commitments between
-  // pi and the n gathered C, so that one subgroup check covers the n + m decoded points
-  const size_t CB = n + (cell ? cell->m : 0), TB = CB + n;  // first C, first tail point
-  const size_t PH = TB + tail;  // GLV: phi(pts[j]) at pts[PH + j]
-  const size_t npts = glv ? 2 * PH : PH;
-  using L = Launch<Cv>;
-  CHK(s.pts.ensure(npts * sizeof(Affine<Cv>)));
-  CHK(s.inf.ensure(npts));
+// What the flags make of a batch of n tuples: its randomisers, whether its MSMs take the GLV
+// form, and where its points go
+struct BatchShape {
+  bool glv;
   // powers: r_i = r^i (255-bit, caller-supplied r).  Fiat-Shamir: r from the transcript, then
   // the seeded 127-bit randomisers with seed = r (so 32n MSM entries, as with a host seed).
-  const bool powers = (flags & KZGMI_FLAG_POWERS) != 0;
-  if (glv) {
+  bool powers;
+  // MSM#1's tail class: -t [1]_1, or for a cell batch (BLS12-381, powers + compressed + subgroup
+  // check) the 64 terms -c_m [tau^m]_1
+  uint32_t tail;
+  // points: [pi (n) | C (n) | tail]; a cell batch keeps its m decoded unique commitments between
+  // pi and the n gathered C, so that one subgroup check covers the n + m decoded points
+  size_t m, CB, TB;  // first C, first tail point
+  size_t PH;         // GLV: phi(pts[j]) at pts[PH + j]
+  size_t npts;
+  int wb;            // window width: H windows for 127-bit magnitudes, F for full scalars
+  uint32_t H, F;     // (c = 16: 8 and 16; c = 13: 10 and 20)
+};
+template <class Cv>
+static BatchShape batch_shape(const kzgmi_ctx* c, size_t n, uint32_t flags, const CellJob* cell) {
+  BatchShape b{};
+  b.glv = c->glv_batch && (Cv::ID == 1 || (flags & (KZGMI_FLAG_SUBGROUP_CHECK | KZGMI_FLAG_TRUSTED_G1)) != 0);
+  b.powers = (flags & KZGMI_FLAG_POWERS) != 0;
+  b.tail = cell ? CellLaunch::TERMS : 1;
+  b.m = cell ? cell->m : 0;
+  b.CB = n + b.m;
+  b.TB = b.CB + n;
+  b.PH = b.TB + b.tail;
+  b.npts = b.glv ? 2 * b.PH : b.PH;
+  b.wb = batch_wbits(c->tune, b.powers, n);
+  b.H = windows_half(b.wb);
+  b.F = windows_full(b.wb);
+  return b;
+}
+
+// the front end's buffers; derived: a blob or cell batch, whose z_i, y_i and r are derived on the
+// device (cell batch: z_k = h_k^64, y_k = 0, r and the 64 coefficients)
+template <class Cv>
+static int ensure_batch_front(Slot& s, const BatchShape& b, size_t n, bool derived, bool cell) {
+  CHK(s.pts.ensure(b.npts * sizeof(Affine<Cv>)));
+  CHK(s.inf.ensure(b.npts));
+  if (b.glv) {
     CHK(s.glv_s.ensure(n * 32));
-    CHK(s.glv_t.ensure((size_t)tail * 32));
-    if (powers) CHK(s.glv_r.ensure(n * 32));
+    CHK(s.glv_t.ensure((size_t)b.tail * 32));
+    if (b.powers) CHK(s.glv_r.ensure(n * 32));
   }
-  CHK(s.scal_r.ensure(n * (powers ? 32 : 16)));
+  CHK(s.scal_r.ensure(n * (b.powers ? 32 : 16)));
   CHK(s.scal_s.ensure(n * 32));
   CHK(s.scal_t.ensure(32));
-  CHK(s.tpart.ensure(L::tpart_bytes((uint32_t)n)));
+  CHK(s.tpart.ensure(Launch<Cv>::tpart_bytes((uint32_t)n)));
   CHK(s.flags.ensure(16));
-  // blob batch (powers mode): z_i, y_i and r are derived on the device, in front(); cell batch:
-  // z_k = h_k^64, y_k = 0, r and the 64 coefficients are
-  if (d_blobs || cell) {
+  if (derived) {
     CHK(s.blob_z.ensure(n * 32));
     CHK(s.blob_y.ensure(n * 32));
-    CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
+    CHK(s.pow.ensure(FS_POW_BITS * sizeof(Fp<typename Cv::FrP>)));
     CHK(s.chal.ensure(32));
     if (cell) {
       CHK(s.cell_part.ensure(CellLaunch::part_bytes()));
       CHK(s.cell_coef.ensure(CellLaunch::TERMS * 32));
     }
+  }
+  return 0;
+}
+
+static BatchScalars batch_scalars(const Slot& s) {
+  return {s.scal_r.as<uint32_t>(), s.scal_s.as<uint32_t>(), s.scal_t.as<uint32_t>(), s.glv_r.as<uint32_t>(),
+          s.glv_s.as<uint32_t>(), s.glv_t.as<uint32_t>(), s.cell_coef.as<uint32_t>()};
+}
+
+// kzgmi_ctx_reserve: a slot's workspace at the sizes of batches of up to n tuples in this mode
+// (msm_plan.hpp plan_reserve); nothing is enqueued
+template <class Cv>
+int HostCore<Cv>::reserve_batch(kzgmi_ctx* c, Slot& s, size_t n, uint32_t flags) {
+  const BatchShape b = batch_shape<Cv>(c, n, flags, nullptr);
+  CHK(ensure_batch_front<Cv>(s, b, n, false, false));
+  // the randomiser workspaces of this mode
+  if (flags & KZGMI_FLAG_FIAT_SHAMIR) CHK(reserve_fs<Cv>(s, n));
+  else if (b.powers) CHK(s.pow.ensure(FS_POW_BITS * sizeof(Fp<typename Cv::FrP>)));
+  const bool own_pts = (flags & (KZGMI_FLAG_COMPRESSED | KZGMI_FLAG_SUBGROUP_CHECK)) != 0;  // (enqueue_batch pts29)
+  return ensure_msm(s, plan_reserve<Cv>(c->tune, b.glv, b.powers, n, own_pts, batch_scalars(s)));
+}
+
+template <class Cv>
+int HostCore<Cv>::enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, const void* dC, const void* dz, const void* dy,
+                  const void* dpi, size_t n, const Seed& seed, uint64_t offset, void* d_partial_out,
+                  uint32_t flags, const void* d_blobs, const CellJob* cell) {
+  using XY = Xyzz<Cv>;
+  using FrF = Fp<typename Cv::FrP>;
+  using L = Launch<Cv>;
+  const BatchShape shape = batch_shape<Cv>(c, n, flags, cell);
+  const bool glv = shape.glv, powers = shape.powers;
+  const uint32_t tail = shape.tail;
+  const size_t CB = shape.CB, TB = shape.TB, PH = shape.PH;
+  CHK(ensure_batch_front<Cv>(s, shape, n, d_blobs || cell, cell != nullptr));
+  if (d_blobs || cell) {
     dz = s.blob_z.p;
     dy = s.blob_y.p;
-  }
-  if (dry) {  // kzgmi_ctx_reserve: the randomiser workspaces of this mode, no launches
-    if (flags & KZGMI_FLAG_FIAT_SHAMIR) CHK(reserve_fs<Cv>(s, n));
-    else if (flags & KZGMI_FLAG_POWERS) CHK(s.pow.ensure(FS_POW_BITS * sizeof(FrF)));
   }
   hipStream_t st = s.stream;
   uint32_t* err = s.flags.template as<uint32_t>() + 1;
@@ -494,55 +451,9 @@ int HostCore<Cv>::enqueue_batch(kzgmi_ctx* c, Slot& s, const kzgmi_srs* srs, con
     mark(c, s, PH_SCALARS + 1);
     return 0;
   };
-  if (!dry) CHK(front());
-  TermList tl{};
-  const uint32_t ph = (uint32_t)PH, cb = (uint32_t)CB, tb = (uint32_t)TB;  // (cb = n, tb = 2n but for cell batches)
-  // c = 16: H = 8 windows for 127-bit magnitudes, F = 16 for full scalars; c = 13: 10 and 20
-  const int wb = call_wbits(c, (size_t)(powers ? 48 : 32) * n, size_t(1) << 22);
-  const uint32_t H = windows_half(wb), F = windows_full(wb);
-  if (glv) {  // every MSM in H windows of half scalars: sets 0..H-1 (MSM#0), H..2H-1 (MSM#1)
-    const uint32_t* rr = s.scal_r.template as<uint32_t>();
-    uint32_t k = 0;
-    if (!powers) {
-      tl.c[k++] = {nn, 0, 4, H, 0, 4, rr};                     // MSM#0: r_i pi_i
-      tl.c[k++] = {nn, nn, 4, H, H, 4, rr};                    // MSM#1: r_i C_i
-    } else {
-      tl.c[k++] = {nn, 0, 4, H, 0, 4, gr};                     // MSM#0: r_i pi_i = h0 pi + h1 phi(pi)
-      tl.c[k++] = {nn, ph, 4, H, 0, 4, gr + 4 * (size_t)n};
-      tl.c[k++] = {nn, cb, 4, H, H, 4, gr};                    // MSM#1: r_i C_i
-      tl.c[k++] = {nn, ph + cb, 4, H, H, 4, gr + 4 * (size_t)n};
-    }
-    tl.c[k++] = {nn, 0, 4, H, H, 4, gs};                       //        s_i pi_i
-    tl.c[k++] = {nn, ph, 4, H, H, 4, gs + 4 * (size_t)n};
-    tl.c[k++] = {tail, tb, 4, H, H, cell ? 4u : 0u, gt};       //        -t G1 (cells: -c_m [tau^m]_1)
-    tl.c[k++] = {tail, ph + tb, 4, H, H, cell ? 4u : 0u, gt + 4 * (size_t)tail};
-    tl.nclass = k;
-    tl.total = 0;
-    for (uint32_t j = 0; j < k; ++j) tl.total += tl.c[j].count;
-    const MsmWindows mw{2, {0, H}, {H, H}};
-    CHK(HostCore<Cv>::run_msm_core(c, s, tl, 2 * H, (size_t)(powers ? 6 : 4) * H * n + 2 * H * tail + 16, mw, nullptr, nullptr,
-                                   pts29, dry, wb));
-  } else if (!powers) {  // 127-bit r_i: MSM#0 in H windows (sets 0..H-1), MSM#1 in F (sets H..H+F-1)
-    tl.c[0] = {nn, 0, 4, H, 0, 4, s.scal_r.template as<uint32_t>()};          // MSM#0: r_i pi_i
-    tl.c[1] = {nn, nn, 4, H, H, 4, s.scal_r.template as<uint32_t>()};         // MSM#1: r_i C_i
-    tl.c[2] = {nn, 0, 8, F, H, 8, s.scal_s.template as<uint32_t>()};          //        s_i pi_i
-    tl.c[3] = {1, 2 * nn, 8, F, H, 0, s.scal_t.template as<uint32_t>()};      //        -t G1
-  }
-  if (!glv && powers) {  // r_i = r^i, full Fr: both MSMs in F windows (sets 0..F-1, F..2F-1)
-    tl.c[0] = {nn, 0, 8, F, 0, 8, s.scal_r.template as<uint32_t>()};
-    tl.c[1] = {nn, cb, 8, F, F, 8, s.scal_r.template as<uint32_t>()};
-    tl.c[2] = {nn, 0, 8, F, F, 8, s.scal_s.template as<uint32_t>()};
-    tl.c[3] = {1, 2 * nn, 8, F, F, 0, s.scal_t.template as<uint32_t>()};
-    if (cell) tl.c[3] = {tail, tb, 8, F, F, 8, s.cell_coef.template as<uint32_t>()};  // -c_m [tau^m]_1
-  }
-  if (!glv) {
-    tl.nclass = 4;
-    tl.total = 3 * nn + tail;
-    const MsmWindows mw = powers ? MsmWindows{2, {0, F}, {F, F}} : MsmWindows{2, {0, H}, {H, F}};
-    CHK(HostCore<Cv>::run_msm_core(c, s, tl, powers ? 2 * F : H + F, (size_t)(powers ? 3 * F : 2 * H + F) * n + (size_t)F * tail + 16, mw,
-                                   nullptr, nullptr, pts29, dry, wb));
-  }
-  if (dry) return 0;
+  CHK(front());
+  const BatchTerms bt = batch_terms(glv, powers, cell ? tail : 0, shape.H, shape.F, n, shape.m, 0, n, true, batch_scalars(s));
+  CHK(HostCore<Cv>::run_msm_core(c, s, bt.tl, bt.nsets, bt.emax, bt.mw, nullptr, nullptr, pts29, shape.wb));
   Roctx rx("kzgmi.batch.pairing");
   if (d_partial_out) {
     L::partial_out(st, s.res.template as<XY>(), 2, err, (XY*)d_partial_out);  // marked if this shard failed
@@ -571,20 +482,12 @@ int HostCore<Cv>::enqueue_batch_chunked(kzgmi_ctx* c, Slot& s, const kzgmi_srs* 
   using XY = Xyzz<Cv>;
   using L = Launch<Cv>;
   using FrF = Fp<typename Cv::FrP>;
-  const bool glv = c->glv_batch && (Cv::ID == 1 || (flags & KZGMI_FLAG_TRUSTED_G1) != 0);
+  const BatchShape shape = batch_shape<Cv>(c, n, flags, nullptr);
+  const bool glv = shape.glv;
+  const int wb = shape.wb;
   const size_t gb = g1_bytes(Cv::ID);
-  const size_t PH = 2 * n + 1;  // GLV: phi(pts[j]) at pts[PH + j]
-  CHK(s.pts.ensure((glv ? 2 * PH : PH) * sizeof(Affine<Cv>)));
-  CHK(s.inf.ensure(glv ? 2 * PH : PH));
-  CHK(s.scal_r.ensure(n * 16));
-  CHK(s.scal_s.ensure(n * 32));
-  CHK(s.scal_t.ensure(32));
-  if (glv) {
-    CHK(s.glv_s.ensure(n * 32));
-    CHK(s.glv_t.ensure(32));
-  }
-  CHK(s.tpart.ensure(L::tpart_bytes((uint32_t)n)));
-  CHK(s.flags.ensure(16));
+  const size_t PH = shape.PH;  // = 2n + 1
+  CHK(ensure_batch_front<Cv>(s, shape, n, false, false));
   CHK(s.stage.ensure(n * (2 * gb + 64)));
   uint8_t* dC = s.stage.template as<uint8_t>();
   uint8_t* dpi = dC + n * gb;
@@ -599,11 +502,6 @@ int HostCore<Cv>::enqueue_batch_chunked(kzgmi_ctx* c, Slot& s, const kzgmi_srs* 
   uint32_t* gt = s.glv_t.template as<uint32_t>();
   FrF* tpart = reinterpret_cast<FrF*>(s.tpart.p);
   uint32_t* err = s.flags.template as<uint32_t>() + 1;
-  const int wb = call_wbits(c, (size_t)32 * n, size_t(1) << 22);
-  const uint32_t H = windows_half(wb), F = windows_full(wb);
-  const MsmWindows mw = glv ? MsmWindows{2, {0, H}, {H, H}} : MsmWindows{2, {0, H}, {H, F}};
-  const uint32_t nsets = glv ? 2 * H : H + F;
-  const uint32_t nn = (uint32_t)n, ph = (uint32_t)PH;
   // the first range short (its copy is the only one nothing overlaps), the others equal
   std::vector<size_t> nk(k);
   {
@@ -614,35 +512,16 @@ int HostCore<Cv>::enqueue_batch_chunked(kzgmi_ctx* c, Slot& s, const kzgmi_srs* 
     for (int j = 1; j < k; ++j) nk[j] = rest[j - 1];
   }
   auto terms = [&](size_t lo, size_t nj, bool last) {
-    TermList tl{};
-    const uint32_t l = (uint32_t)lo, m = (uint32_t)nj;
-    uint32_t q = 0;
-    tl.c[q++] = {m, l, 4, H, 0, 4, sr + 4 * lo};           // MSM#0: r_i pi_i
-    tl.c[q++] = {m, nn + l, 4, H, H, 4, sr + 4 * lo};      // MSM#1: r_i C_i
-    if (glv) {
-      tl.c[q++] = {m, l, 4, H, H, 4, gs + 4 * lo};         //        s_i pi_i = h0 pi + h1 phi(pi)
-      tl.c[q++] = {m, ph + l, 4, H, H, 4, gs + 4 * (n + lo)};
-      if (last) {
-        tl.c[q++] = {1, 2 * nn, 4, H, H, 0, gt};           //        -t G1
-        tl.c[q++] = {1, ph + 2 * nn, 4, H, H, 0, gt + 4};
-      }
-    } else {
-      tl.c[q++] = {m, l, 8, F, H, 8, ss + 8 * lo};         //        s_i pi_i
-      if (last) tl.c[q++] = {1, 2 * nn, 8, F, H, 0, stt};  //        -t G1
-    }
-    tl.nclass = q;
-    tl.total = 0;
-    for (uint32_t j = 0; j < q; ++j) tl.total += tl.c[j].count;
-    return tl;
-  };
-  auto emax_of = [&](size_t nj) {
-    return glv ? (size_t)4 * H * nj + 2 * H + 16 : (size_t)(2 * H + F) * nj + F + 16;
+    return batch_terms(glv, false, 0, shape.H, shape.F, n, 0, lo, nj, last, batch_scalars(s));
   };
   size_t nmax = 0;
   for (size_t v : nk) nmax = std::max(nmax, v);
   // every workspace at its final size before the first launch (a later growth would free a buffer
-  // an earlier range's kernels are still using)
-  CHK(HostCore<Cv>::run_msm_core(c, s, terms(0, nmax, true), nsets, emax_of(nmax), mw, nullptr, nullptr, true, true, wb, 3));
+  // an earlier range's kernels are still using): the plan of the largest range as a last one
+  {
+    const BatchTerms bt = terms(0, nmax, true);
+    CHK(ensure_msm(s, plan_msm<Cv>(c->tune, bt.tl, bt.nsets, bt.emax, bt.mw, wb, 3, false, /*alone=*/true, c->sync_call)));
+  }
   hipStream_t st = s.stream, cs = c->h2d_stream;
   if (s.done_rec) HIPCHK(hipStreamWaitEvent(cs, s.done_ev, 0));  // the stage buffer is free
   size_t lo = 0;
@@ -679,7 +558,8 @@ int HostCore<Cv>::enqueue_batch_chunked(kzgmi_ctx* c, Slot& s, const kzgmi_srs* 
       if (glv) L::glv_split(st, stt, 8, 1, gt, gt + 4);
     }
     const int part = k == 1 ? 0 : j == 0 ? 1 : last ? 3 : 2;
-    CHK(HostCore<Cv>::run_msm_core(c, s, terms(lo, nj, last), nsets, emax_of(nj), mw, nullptr, nullptr, true, false, wb, part));
+    const BatchTerms bt = terms(lo, nj, last);
+    CHK(HostCore<Cv>::run_msm_core(c, s, bt.tl, bt.nsets, bt.emax, bt.mw, nullptr, nullptr, true, wb, part));
     lo += nj;
   }
   L::pairing_check(st, s.res.template as<XY>(), srs->lines.template as<Line<Cv>>(), srs->q_inf.template as<uint8_t>(),
@@ -721,7 +601,7 @@ int HostCore<Cv>::enqueue_msm(kzgmi_ctx* c, Slot& s, const void* dpts, const voi
   mark(c, s, PH_SCALARS + 1);
   TermList tl{};
   const uint32_t nn = (uint32_t)n;
-  const int wb = call_wbits(c, (size_t)16 * n, size_t(1) << 21);
+  const int wb = call_wbits(c->tune, (size_t)16 * n, size_t(1) << 21);
   const uint32_t H = windows_half(wb), F = windows_full(wb);
   if (glv) {  // sum k_i P_i = sum h0_i P_i + h1_i phi(P_i): H windows, H bucket sets
     tl.c[0] = {nn, 0, 4, H, 0, 4, gs};
@@ -729,13 +609,13 @@ int HostCore<Cv>::enqueue_msm(kzgmi_ctx* c, Slot& s, const void* dpts, const voi
     tl.nclass = 2;
     tl.total = 2 * nn;
     const MsmWindows mw{1, {0, 0}, {H, 0}};
-    CHK(HostCore<Cv>::run_msm_core(c, s, tl, H, (size_t)2 * H * n + 16, mw, nullptr, nullptr, pts29, false, wb));
+    CHK(HostCore<Cv>::run_msm_core(c, s, tl, H, (size_t)2 * H * n + 16, mw, nullptr, nullptr, pts29, wb));
   } else {
     tl.c[0] = {nn, 0, 8, F, 0, 8, sc};
     tl.nclass = 1;
     tl.total = nn;
     const MsmWindows mw{1, {0, 0}, {F, 0}};
-    CHK(HostCore<Cv>::run_msm_core(c, s, tl, F, (size_t)F * n + 16, mw, nullptr, nullptr, pts29, false, wb));
+    CHK(HostCore<Cv>::run_msm_core(c, s, tl, F, (size_t)F * n + 16, mw, nullptr, nullptr, pts29, wb));
   }
   s.curve = Cv::ID;
   return 0;

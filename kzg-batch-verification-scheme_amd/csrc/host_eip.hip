@@ -90,7 +90,7 @@ int kzgmi_verify_blob_batch_device_async(kzgmi_ctx* c, const kzgmi_srs* srs, int
   Roctx rx("kzgmi_verify_blob_batch_device_async");
   CHK(ensure_blob_table(c, s.stream));
   return HostCore<Bls12_381>::enqueue_batch(c, s, srs, d_commitments48, nullptr, nullptr, d_proofs48, n, Seed{}, 0, nullptr,
-                                            kBlobFlags, /*dry=*/false, d_blobs);
+                                            kBlobFlags, d_blobs);
 }
 
 int kzgmi_verify_blob_batch_device(kzgmi_ctx* c, const kzgmi_srs* srs, const void* d_blobs,
@@ -293,7 +293,7 @@ int kzgmi_verify_cell_batch_device_async(kzgmi_ctx* c, const kzgmi_cell_srs* csr
     CHK(ensure_cell_table(c, s.stream));
     const CellJob job{csrs, d_commitment_indices, d_cell_indices, d_cells, m, r32 == nullptr};
     return HostCore<Bls12_381>::enqueue_batch(c, s, csrs->srs, d_commitments48, nullptr, nullptr, d_proofs48, n, seed_of(r32), 0,
-                                              nullptr, kBlobFlags, /*dry=*/false, nullptr, &job);
+                                              nullptr, kBlobFlags, nullptr, &job);
   }
 }
 

@@ -89,7 +89,7 @@ constexpr int BINS_PER_SET = NBUCKETS >> COARSE_SHIFT;  // 256
 constexpr int TILE_TERMS = 4096;                        // terms per tile (16 per thread)
 // Window width c of a call (WBITS, NBUCKETS, BINS_PER_SET above are c = 16's): large calls use
 // c = 16; small ones (few entries per bucket) c = 13 -- 8x fewer buckets to reduce for 5/4 the
-// terms (host_core.hip call_wbits).  The sort, the window-sum reduction and the combination are
+// terms (msm_plan.hpp call_wbits).  The sort, the window-sum reduction and the combination are
 // instantiated per c.
 template <int C>
 struct Win {

@@ -311,8 +311,9 @@ def test_two_rank_gloo_pipeline_on_gpu():
 @pytest.mark.parametrize("curve,mode", [("bls12_381", {}), ("bls12_381", {"trusted_g1": True}),
                                         ("bls12_381", {"fiat_shamir": True}), ("bn254", {})])
 def test_reserve_leaves_nothing_to_allocate(curve, mode):
-    """kzgmi_ctx_reserve sizes every slot for the mode: pipelined batches of at most that size then
-    make no workspace allocation (kzgmi_alloc_count unchanged), and verify as the oracle does."""
+    """kzgmi_ctx_reserve sizes every slot for the mode: pipelined batches of at most that size, one
+    small enough for the one-wave-per-term form among them, then make no workspace allocation
+    (kzgmi_alloc_count unchanged), and verify as the oracle does."""
     import kzgmi
     n, slots = 5000, 3
     c = kzgmi.Context(0, slots)
@@ -330,6 +331,8 @@ def test_reserve_leaves_nothing_to_allocate(curve, mode):
             c.batch_verify_async(srs, s, Cm, z, y, P, n if k % 2 == 0 else n - 17, seed=seed, **mode)
         for s in range(slots):
             assert c.wait(s)
+        c.batch_verify_async(srs, 0, Cm, z, y, P, 256, seed=seed, **mode)  # the small form: its tree is reserved too
+        assert c.wait(0)
         assert kzgmi.alloc_count() == a0, "a reserved context allocated inside the steady state"
         c.batch_verify_async(srs, 0, Cm, z, y, P, n, seed=seed, **mode)  # still accepts after the reuse
         assert c.wait(0)

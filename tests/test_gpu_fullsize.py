@@ -162,7 +162,7 @@ def test_sharded_batch_cfg5_bn254(ctx):
 
 @pytest.mark.parametrize("curve,n,trusted", [("bls12_381", 300007, False), ("bls12_381", 262143, True),
                                              ("bn254", 524289, False),
-                                             # 2^15 < n <= 2^17: 13-bit windows (host_core.hip call_wbits)
+                                             # 2^15 < n <= 2^17: 13-bit windows (msm_plan.hpp call_wbits)
                                              ("bls12_381", 100003, False), ("bls12_381", 70001, True),
                                              ("bn254", 90001, False)])
 def test_ragged_batch_vs_oracle(ctx, curve, n, trusted):
@@ -222,7 +222,7 @@ def test_ragged_msm_vs_oracle(ctx, curve, n, trusted):
 
 # the path switches of a batch call: the one-wave-per-term small path up to 4096 MSM terms (3n + 1
 # for BLS12-381, 4n + 2 for BN254's GLV halves), 13-bit windows from 2^15 + 1 tuples, 16-bit
-# windows and the 2^23-entry accumulation order depth above 2^17 (host_core.hip run_msm_core, call_wbits)
+# windows and the 2^23-entry accumulation order depth above 2^17 (host_core.hip run_msm_core, msm_plan.hpp call_wbits)
 @pytest.mark.parametrize("curve,n", [("bls12_381", 1365), ("bls12_381", 1366), ("bls12_381", 32768),
                                      ("bls12_381", 32769), ("bls12_381", 131072), ("bls12_381", 131073),
                                      ("bn254", 1023), ("bn254", 1024), ("bn254", 32769)])
@@ -264,7 +264,7 @@ def _context_env(slots, **env):
 def test_split_accumulation_vs_oracle(curve, log_n):
     """The split accumulation (host_core.hip run_msm_core): MSM#0's bucket sets accumulate in one
     launch, then MSM#1's in a second one over the sorted range after them, while MSM#0's
-    reduction and window combination run on the slot's side stream.  Forced on
+    reduction and window combination run on the context's one side stream.  Forced on
     (KZGMI_SPLIT_ACC=1) and off (=0): A, B and the verdict bit-exact vs the oracle, a corrupted
     y flips the verdict; the split with the first launch's piece joins on the slot stream and the
     side stream at the slot's priority (KZGMI_SPLIT_SIDEFIX=0, KZGMI_SPLIT_SIDEPRIO=0); the
