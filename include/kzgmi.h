@@ -66,7 +66,9 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * blob entry points kzgmi_blob_*_device and kzgmi_verify_blob_batch* were added; still 6 (additive):
  * the EIP-7594 cell entry points kzgmi_cell_* and kzgmi_verify_cell_batch*, and the cell extension
  * and recovery entry points kzgmi_compute_cells* and kzgmi_recover_cells*, and the cell proof entry
- * points kzgmi_cell_pk_*, kzgmi_*_cells_and_proofs*, kzgmi_fk20_scalars_device, kzgmi_g1_fft128_device.
+ * points kzgmi_cell_pk_*, kzgmi_*_cells_and_proofs*, kzgmi_fk20_scalars_device, kzgmi_g1_fft128_device,
+ * and the EIP-4844 producer entry points kzgmi_blob_pk_*, kzgmi_blob_commit*, kzgmi_compute_kzg_proofs*,
+ * kzgmi_compute_blob_proofs*, kzgmi_blob_quotient_device.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -296,6 +298,63 @@ int kzgmi_verify_blob_batch_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const v
 int kzgmi_verify_blob_batch_device_async(kzgmi_ctx* ctx, const kzgmi_srs* srs, int slot,
                                          const void* d_blobs, const void* d_commitments48,
                                          const void* d_proofs48, size_t n);
+
+/* ---- EIP-4844 commitments and proofs (Deneb polynomial-commitments blob_to_kzg_commitment,
+ * compute_kzg_proof, compute_blob_kzg_proof) -- BLS12-381 only, with the blob conventions above.
+ * With v_j = blob element j = p(dom[j]) and L_j = [l_j(tau)]_1 for the Lagrange polynomial l_j of dom[j]:
+ *     commitment = sum_j v_j L_j
+ *     y = p(z),  q_j = (v_j - y) / (dom[j] - z),  proof = sum_j q_j L_j       (q = (p - y) / (X - z) on dom)
+ *     z = dom[m]:  y = v_m,  q_m = sum_{i != m} (v_i - y) dom[i] / (z (z - dom[i]))
+ * Both sums are one fixed-base MSM over the blob proof key: the 4096 points as a table of window
+ * multiples (kzgmi_blob_pk_device_bytes: 256 MiB, 4096 x 64 x 8 rows of 96 B in 128 B slots, plus one
+ * flag byte per point), batched over the nb blobs of a call.
+ * g1_lagrange: 4096 x 96 B uncompressed, point j = L_j (the trusted setup's Lagrange points in
+ * bit-reversed order).  Validated like kzgmi_cell_pk_load's points: encoding, on curve, in G1, each
+ * with its own code; the point at infinity: KZGMI_ERR_ARG.  The loader does not (cannot) check that
+ * the points are a Lagrange basis: it is a fixed-base key over any 4096 G1 points.  The key lives on
+ * the context's primary device and works with that device's slots only; a key of another context:
+ * KZGMI_ERR_ARG.
+ * blob_commit: nb blobs -> nb x 48 B ZCash compressed commitments (infinity: 0xC0 and 47 zero bytes).
+ * compute_kzg_proofs: zs nb x 32 B big-endian (z >= r: KZGMI_ERR_SCALAR) -> proofs nb x 48 B and
+ * ys nb x 32 B; any z < r, points of the domain included.
+ * compute_blob_proofs: commitments nb x 48 B, decoded and subgroup-checked with
+ * KZGMI_FLAG_COMPRESSED | KZGMI_FLAG_SUBGROUP_CHECK semantics and error codes; z_i is the blob's
+ * challenge, hashed on the device -> proofs nb x 48 B (what kzgmi_verify_blob_batch accepts).
+ * A blob element >= r: KZGMI_ERR_SCALAR.  nb == 0 succeeds and writes nothing; nb > 4096:
+ * KZGMI_ERR_ARG.  Device arrays are 16-byte aligned; outputs overlap neither the inputs nor each
+ * other.  The host forms stage through slot 0 and copy the results back; the synchronous device forms
+ * run on slot 0; the async forms run on any slot and complete with kzgmi_slot_wait (ok_out = 1), which
+ * reports the device-side errors.  A call that fails writes no output and leaves its slot usable.
+ * Scratch (the quotients at nb x 128 KiB, the partial sums, the decoded commitments) lives in the
+ * slot's workspace (grown on first use, counted by kzgmi_alloc_count). */
+typedef struct kzgmi_blob_pk kzgmi_blob_pk;
+int kzgmi_blob_pk_load(kzgmi_ctx* ctx, const uint8_t* g1_lagrange, kzgmi_blob_pk** out);
+void kzgmi_blob_pk_free(kzgmi_blob_pk* pk);
+size_t kzgmi_blob_pk_device_bytes(const kzgmi_blob_pk* pk);
+int kzgmi_blob_commit(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, const uint8_t* blobs, size_t nb,
+                      uint8_t* commitments48_out);
+int kzgmi_blob_commit_device(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, const void* d_blobs, size_t nb,
+                             void* d_commitments48_out);
+int kzgmi_blob_commit_device_async(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, int slot, const void* d_blobs, size_t nb,
+                                   void* d_commitments48_out);
+int kzgmi_compute_kzg_proofs(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, const uint8_t* blobs, const uint8_t* zs,
+                             size_t nb, uint8_t* proofs48_out, uint8_t* ys_out);
+int kzgmi_compute_kzg_proofs_device(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, const void* d_blobs, const void* d_zs,
+                                    size_t nb, void* d_proofs48_out, void* d_ys_out);
+int kzgmi_compute_kzg_proofs_device_async(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, int slot, const void* d_blobs,
+                                          const void* d_zs, size_t nb, void* d_proofs48_out, void* d_ys_out);
+int kzgmi_compute_blob_proofs(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, const uint8_t* blobs,
+                              const uint8_t* commitments48, size_t nb, uint8_t* proofs48_out);
+int kzgmi_compute_blob_proofs_device(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, const void* d_blobs,
+                                     const void* d_commitments48, size_t nb, void* d_proofs48_out);
+int kzgmi_compute_blob_proofs_device_async(kzgmi_ctx* ctx, const kzgmi_blob_pk* pk, int slot, const void* d_blobs,
+                                           const void* d_commitments48, size_t nb, void* d_proofs48_out);
+/* Diagnostic (synchronous, slot 0), like kzgmi_blob_eval_device: y_i = p_i(z_i) -> d_ys_out (nb x 32 B)
+ * and the quotient's evaluations q_i -> d_q_out (nb x 128 KiB, 32 B big-endian each, blob layout).
+ * Unlike the calls above it writes straight to the caller's arrays, which it does not check for
+ * overlap: on an error (an element or z >= r) their contents are unspecified. */
+int kzgmi_blob_quotient_device(kzgmi_ctx* ctx, const void* d_blobs, const void* d_zs, size_t nb, void* d_ys_out,
+                               void* d_q_out);
 
 /* ---- EIP-7594 cell batches (PeerDAS polynomial-commitments-sampling verify_cell_kzg_proof_batch) --
  * BLS12-381 only.  r is the scalar modulus, w = 7^((r-1)/8192) (its square is the blob domain's

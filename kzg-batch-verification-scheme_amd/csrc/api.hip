@@ -413,6 +413,11 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
     pk->tab_inf.release();
     pk->ctx = nullptr;
   }
+  for (kzgmi_blob_pk* pk : c->blob_pk_list) {  // detach: later kzgmi_blob_pk_free() only deletes the struct
+    pk->tab.release();
+    pk->tab_inf.release();
+    pk->ctx = nullptr;
+  }
   for (kzgmi_ck* ck : c->ck_list) {  // detach: later kzgmi_ck_free() only deletes the struct
     ck->pts.release();
     ck->inf.release();

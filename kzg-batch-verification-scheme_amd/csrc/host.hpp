@@ -103,6 +103,7 @@ struct Slot {
   DevBuf cell_part, cell_coef;                   // cell batches: per-coset coefficients; -c_m (64 x 8 LE words)
   DevBuf rec_z;                                  // recover_cells: the call's vanishing-polynomial table (recover.hpp)
   DevBuf fk_coef, fk_scal, fk_a, fk_b, fk_enc;   // cell proofs (fk20.hpp): coefficients, ahat, two point vectors, encodings
+  DevBuf bp_q, bp_part, bp_enc;                  // blob proofs (blobproof.hpp): quotients, partial sums and results, encodings
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -130,7 +131,7 @@ struct Slot {
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
                       &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z,
-                      &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc};
+                      &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc};
     for (DevBuf* b : bufs) f(*b);
   }
 };
@@ -140,6 +141,7 @@ using namespace kzgmi;
 
 struct kzgmi_cell_srs;
 struct kzgmi_cell_pk;
+struct kzgmi_blob_pk;
 
 struct kzgmi_ctx {
   int device = 0;
@@ -209,6 +211,7 @@ struct kzgmi_ctx {
   std::vector<kzgmi_ck*> ck_list;    // live commit keys: same
   std::vector<kzgmi_cell_srs*> cell_srs_list;  // live cell SRS objects: same (their inner kzgmi_srs is in srs_list)
   std::vector<kzgmi_cell_pk*> cell_pk_list;    // live cell proof keys: same
+  std::vector<kzgmi_blob_pk*> blob_pk_list;    // live blob proof keys: same
 };
 
 // prover commit key: rows w = 0..15 of 2^(16 w)-shifted SRS points, [row][point] Montgomery affine
@@ -244,6 +247,13 @@ struct kzgmi_cell_pk {
   kzgmi_ctx* ctx = nullptr;
   DevBuf tab;                       // [base][window][multiple] Montgomery affine
   DevBuf tab_inf;                   // per base: xhat[base] is the point at infinity
+};
+
+// EIP-4844 blob proof key (blobproof.hpp): the 4096 Lagrange points as a table of window multiples
+struct kzgmi_blob_pk {
+  kzgmi_ctx* ctx = nullptr;
+  DevBuf tab;                       // [base][window][multiple] Montgomery affine
+  DevBuf tab_inf;                   // per base: the point at infinity (all zero: checked at load)
 };
 
 namespace kzgmi {

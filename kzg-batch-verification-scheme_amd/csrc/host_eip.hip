@@ -1,5 +1,6 @@
 // The Ethereum front ends (BLS12-381 only): EIP-4844 blob batches, EIP-7594 cell batches, cell
-// extension / recovery and cell proof generation (FK20), with their utilities.
+// extension / recovery, cell proof generation (FK20) and EIP-4844 commitments and proofs, with their
+// utilities.
 #include "host.hpp"
 
 namespace {
@@ -672,6 +673,259 @@ int kzgmi_g1_fft128_device(kzgmi_ctx* c, const void* d_points96, size_t count, i
     if (inverse) Fk20Launch::scale128(st, a, n);
     Fk20Launch::unrev(st, a, cnt, b);
     L::encode_points(st, b, n, (uint8_t*)d_out96);
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------------------ EIP-4844 commitments and proofs
+}  // extern "C"
+namespace {
+// blob_to_kzg_commitment; compute_kzg_proof (in2 = zs, out2 = ys); compute_blob_kzg_proof (in2 = commitments)
+enum class BlobOp { Commit, Proofs, BlobProofs };
+
+int check_blob_pk(const kzgmi_ctx* c, const kzgmi_blob_pk* pk) {
+  if (!pk || std::find(c->blob_pk_list.begin(), c->blob_pk_list.end(), pk) == c->blob_pk_list.end())
+    return fail(KZGMI_ERR_ARG, "not a blob proof key of this context (kzgmi_blob_pk_load)");
+  return 0;
+}
+
+size_t blob_in2_bytes(BlobOp op, size_t nb) { return op == BlobOp::Proofs ? 32 * nb : op == BlobOp::BlobProofs ? 48 * nb : 0; }
+size_t blob_out2_bytes(BlobOp op, size_t nb) { return op == BlobOp::Proofs ? 32 * nb : 0; }
+
+// The argument checks every form shares
+int check_blob_args(BlobOp op, const void* d_blobs, const void* d_in2, size_t nb, const void* d_out, const void* d_out2,
+                    bool device) {
+  if (nb > kRecoverMaxBlobs) return fail(KZGMI_ERR_ARG, "too many blobs (max 4096 per call)");
+  const size_t in2 = blob_in2_bytes(op, nb), out2 = blob_out2_bytes(op, nb);
+  if (nb && (!d_blobs || !d_out || (in2 && !d_in2) || (out2 && !d_out2))) return fail(KZGMI_ERR_ARG, "null argument");
+  if (!device || nb == 0) return 0;
+  if (((uintptr_t)d_blobs | (uintptr_t)d_out | (in2 ? (uintptr_t)d_in2 : 0) | (out2 ? (uintptr_t)d_out2 : 0)) & 15)
+    return fail(KZGMI_ERR_ARG, "device arrays must be 16-byte aligned");
+  const size_t bb = nb * BlobLaunch::BYTES, ob = 48 * nb;
+  if (ranges_overlap(d_blobs, bb, d_out, ob) || (in2 && ranges_overlap(d_in2, in2, d_out, ob)) ||
+      (out2 && (ranges_overlap(d_blobs, bb, d_out2, out2) || ranges_overlap(d_in2, in2, d_out2, out2) ||
+                ranges_overlap(d_out, ob, d_out2, out2))))
+    return fail(KZGMI_ERR_ARG, "the output overlaps an input or the other output");
+  return 0;
+}
+
+// One commitment / proof job on slot s (any slot of the key's device): completes with kzgmi_slot_wait
+// like enqueue_cells_job, its kernels reporting through the slot's error word.  d_out (nb x 48 B) and
+// d_out2 are written by the emit kernels only, which write nothing once an error is raised.
+int enqueue_blob_job(kzgmi_ctx* c, Slot& s, const kzgmi_blob_pk* pk, BlobOp op, const void* d_blobs, const void* d_in2,
+                     size_t nb, void* d_out, void* d_out2) {
+  using L = Launch<Bls12_381>;
+  using XY = Xyzz<Bls12_381>;
+  using AF = Affine<Bls12_381>;
+  if (s.pending) return fail(KZGMI_ERR_ARG, "slot busy: call kzgmi_slot_wait first");
+  if (nb == 0) return arm_empty(s, JobKind::Utility, 0);  // succeeds, writes nothing
+  const uint32_t n = (uint32_t)nb;
+  CHK(s.flags.ensure(16));
+  CHK(s.bp_part.ensure((size_t)n * (BlobProofLaunch::PARTS + 1) * sizeof(XY)));  // the partials, then the sums
+  CHK(s.bp_enc.ensure((size_t)n * (96 + 48)));
+  if (op != BlobOp::Commit) {
+    CHK(s.bp_q.ensure(nb * BlobLaunch::BYTES));
+    CHK(s.blob_y.ensure(nb * 32));
+    CHK(ensure_blob_table(c, s.stream));
+  }
+  if (op == BlobOp::BlobProofs) {
+    CHK(s.pts.ensure(nb * sizeof(AF)));
+    CHK(s.inf.ensure(nb));
+    CHK(s.blob_z.ensure(nb * 32));
+  }
+  CHK(begin_job(s));
+  hipStream_t st = s.stream;
+  HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, st));
+  uint32_t* err = s.flags.template as<uint32_t>() + 1;
+  const uint8_t* blobs = (const uint8_t*)d_blobs;
+  const uint8_t* scal = blobs;  // the commitment's scalars are the blob's bytes
+  if (op != BlobOp::Commit) {
+    const uint8_t* zs = (const uint8_t*)d_in2;
+    if (op == BlobOp::BlobProofs) {  // the commitments decoded and checked as a verifier would; z_i from the blob hash
+      AF* pts = s.pts.template as<AF>();
+      uint8_t* inf = s.inf.template as<uint8_t>();
+      L::decompress_points(st, (const uint8_t*)d_in2, n, pts, inf, err);
+      L::subgroup_check(st, pts, inf, n, err);
+      BlobLaunch::challenges(st, blob_mapping(c, nb), blobs, (const uint8_t*)d_in2, n, s.blob_z.template as<uint8_t>(), err);
+      zs = s.blob_z.template as<uint8_t>();
+    }
+    BlobProofLaunch::quotient(st, blobs, zs, c->blob_table.p, n, op == BlobOp::Proofs, s.blob_y.template as<uint8_t>(),
+                              s.bp_q.template as<uint8_t>(), err);
+    scal = s.bp_q.template as<uint8_t>();
+  }
+  XY* parts = s.bp_part.template as<XY>();
+  XY* res = parts + (size_t)n * BlobProofLaunch::PARTS;
+  uint8_t* enc = s.bp_enc.template as<uint8_t>();
+  uint8_t* enc48 = enc + (size_t)n * 96;
+  BlobProofLaunch::msm(st, scal, n, op == BlobOp::Commit, pk->tab.p, pk->tab_inf.template as<uint8_t>(), parts, res, err);
+  L::encode_points(st, res, n, enc);
+  L::compress_points(st, enc, n, enc48);
+  Fk20Launch::emit(st, enc48, (size_t)n * 48, err, d_out);
+  if (op == BlobOp::Proofs) Fk20Launch::emit(st, s.blob_y.p, (size_t)n * 32, err, d_out2);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, st));
+  CHK(end_job(s));
+  arm(s, JobKind::Utility, 0);
+  return 0;
+}
+
+int blob_job_async(kzgmi_ctx* c, const kzgmi_blob_pk* pk, int slot, const char* name, BlobOp op, const void* d_blobs,
+                   const void* d_in2, size_t nb, void* d_out, void* d_out2) {
+  KZ_ROUTE(c, nullptr, slot);  // (proof keys live on the primary device: its slots only)
+  CHK(check_ctx(c, slot));
+  CHK(check_blob_pk(c, pk));
+  CHK(check_blob_args(op, d_blobs, d_in2, nb, d_out, d_out2, true));
+  Roctx rx(name);
+  return enqueue_blob_job(c, c->slots[slot], pk, op, d_blobs, d_in2, nb, d_out, d_out2);
+}
+
+// The host form of each: [blobs | zs or commitments | out | ys] in slot 0's stage buffer, the results copied back
+int blob_job_host(kzgmi_ctx* c, const kzgmi_blob_pk* pk, BlobOp op, const uint8_t* blobs, const uint8_t* in2, size_t nb,
+                  uint8_t* out, uint8_t* out2) {
+  CHK(check_ctx(c));
+  CHK(check_blob_pk(c, pk));
+  CHK(check_blob_args(op, blobs, in2, nb, out, out2, false));
+  CHK(slot0_idle(c));
+  if (nb == 0) return 0;
+  Slot& s = c->slots[0];
+  const size_t ib = blob_in2_bytes(op, nb), ob = blob_out2_bytes(op, nb);
+  const StageItem items[4] = {{blobs, nb * BlobLaunch::BYTES}, {ib ? in2 : nullptr, ib}, {nullptr, 48 * nb}, {nullptr, ob}};
+  uint8_t* d[4];
+  CHK(stage_host(c, s, items, 4, d));
+  CHK(enqueue_blob_job(c, s, pk, op, d[0], d[1], nb, d[2], d[3]));
+  CHK(finish_slot(c, s, nullptr));
+  HIPCHK(hipMemcpy(out, d[2], 48 * nb, hipMemcpyDeviceToHost));
+  if (ob) HIPCHK(hipMemcpy(out2, d[3], ob, hipMemcpyDeviceToHost));
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+void kzgmi_blob_pk_free(kzgmi_blob_pk* pk) {
+  if (!pk) return;
+  if (kzgmi_ctx* c = pk->ctx) {
+    (void)hipSetDevice(c->device);
+    auto& v = c->blob_pk_list;
+    v.erase(std::remove(v.begin(), v.end(), pk), v.end());
+    pk->tab.release();
+    pk->tab_inf.release();
+  }
+  delete pk;
+}
+
+size_t kzgmi_blob_pk_device_bytes(const kzgmi_blob_pk* pk) { return pk ? pk->tab.cap + pk->tab_inf.cap : 0; }
+
+int kzgmi_blob_pk_load(kzgmi_ctx* c, const uint8_t* g1_lagrange, kzgmi_blob_pk** out) {
+  CHK(check_ctx(c));
+  if (!g1_lagrange || !out) return fail(KZGMI_ERR_ARG, "null blob proof key argument");
+  *out = nullptr;
+  CHK(slot0_idle(c));
+  using Cv = Bls12_381;
+  using L = Launch<Cv>;
+  constexpr uint32_t T = BlobProofLaunch::POINTS;
+  Slot& s = c->slots[0];
+  kzgmi_blob_pk* pk = new kzgmi_blob_pk();
+  DevBuf pts, inf;  // the validated points: needed while the table is built
+  auto undo = [&](int rc) {
+    pts.release();
+    inf.release();
+    pk->tab.release();
+    pk->tab_inf.release();
+    delete pk;
+    return rc;
+  };
+  int r = 0;
+  if ((r = s.stage.ensure(T * 96)) || (r = s.flags.ensure(16)) || (r = pts.ensure(T * sizeof(Affine<Cv>))) ||
+      (r = inf.ensure(T)) || (r = pk->tab.ensure(BlobProofLaunch::table_bytes())) ||
+      (r = pk->tab_inf.ensure(BlobProofLaunch::table_flags())) || (r = begin_job(s)))
+    return undo(r);
+  hipStream_t st = s.stream;
+  std::vector<uint8_t> inf_h(T);
+  bool okk = hipMemcpyAsync(s.stage.p, g1_lagrange, T * 96, hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemsetAsync(s.flags.p, 0, 16, st) == hipSuccess;
+  if (okk) {  // validated like any input point, and in G1 (the table's rows rely on the order r)
+    uint32_t* err = s.flags.template as<uint32_t>() + 1;
+    Affine<Cv>* p = pts.template as<Affine<Cv>>();
+    L::convert_points(st, s.stage.template as<uint8_t>(), T, p, inf.template as<uint8_t>(), err);
+    L::subgroup_check(st, p, inf.template as<uint8_t>(), T, err);
+    BlobProofLaunch::key(st, p, inf.template as<uint8_t>(), pk->tab.p, pk->tab_inf.template as<uint8_t>());
+    okk = hipGetLastError() == hipSuccess &&
+          hipMemcpyAsync(s.host_flags, s.flags.p, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(inf_h.data(), inf.p, T, hipMemcpyDeviceToHost, st) == hipSuccess && sync_job(s) == 0;
+  }
+  if (!okk) return undo(fail(KZGMI_ERR_DEVICE, "blob proof key upload/precompute failed"));
+  int e = map_device_err((uint32_t)s.host_flags[1]);
+  for (uint32_t k = 0; !e && k < T; ++k)
+    if (inf_h[k]) e = fail(KZGMI_ERR_ARG, "blob proof key G1 element is the point at infinity");
+  if (e) return undo(e);
+  pts.release();
+  inf.release();
+  pk->ctx = c;
+  c->blob_pk_list.push_back(pk);
+  *out = pk;
+  return 0;
+}
+
+int kzgmi_blob_commit_device_async(kzgmi_ctx* c, const kzgmi_blob_pk* pk, int slot, const void* d_blobs, size_t nb,
+                                   void* d_commitments48_out) {
+  return blob_job_async(c, pk, slot, "kzgmi_blob_commit_device_async", BlobOp::Commit, d_blobs, nullptr, nb,
+                        d_commitments48_out, nullptr);
+}
+
+int kzgmi_blob_commit_device(kzgmi_ctx* c, const kzgmi_blob_pk* pk, const void* d_blobs, size_t nb,
+                             void* d_commitments48_out) {
+  return run_slot0(c, [&] { return kzgmi_blob_commit_device_async(c, pk, 0, d_blobs, nb, d_commitments48_out); });
+}
+
+int kzgmi_blob_commit(kzgmi_ctx* c, const kzgmi_blob_pk* pk, const uint8_t* blobs, size_t nb, uint8_t* commitments48_out) {
+  return blob_job_host(c, pk, BlobOp::Commit, blobs, nullptr, nb, commitments48_out, nullptr);
+}
+
+int kzgmi_compute_kzg_proofs_device_async(kzgmi_ctx* c, const kzgmi_blob_pk* pk, int slot, const void* d_blobs,
+                                          const void* d_zs, size_t nb, void* d_proofs48_out, void* d_ys_out) {
+  return blob_job_async(c, pk, slot, "kzgmi_compute_kzg_proofs_device_async", BlobOp::Proofs, d_blobs, d_zs, nb,
+                        d_proofs48_out, d_ys_out);
+}
+
+int kzgmi_compute_kzg_proofs_device(kzgmi_ctx* c, const kzgmi_blob_pk* pk, const void* d_blobs, const void* d_zs,
+                                    size_t nb, void* d_proofs48_out, void* d_ys_out) {
+  return run_slot0(
+      c, [&] { return kzgmi_compute_kzg_proofs_device_async(c, pk, 0, d_blobs, d_zs, nb, d_proofs48_out, d_ys_out); });
+}
+
+int kzgmi_compute_kzg_proofs(kzgmi_ctx* c, const kzgmi_blob_pk* pk, const uint8_t* blobs, const uint8_t* zs, size_t nb,
+                             uint8_t* proofs48_out, uint8_t* ys_out) {
+  return blob_job_host(c, pk, BlobOp::Proofs, blobs, zs, nb, proofs48_out, ys_out);
+}
+
+int kzgmi_compute_blob_proofs_device_async(kzgmi_ctx* c, const kzgmi_blob_pk* pk, int slot, const void* d_blobs,
+                                           const void* d_commitments48, size_t nb, void* d_proofs48_out) {
+  return blob_job_async(c, pk, slot, "kzgmi_compute_blob_proofs_device_async", BlobOp::BlobProofs, d_blobs,
+                        d_commitments48, nb, d_proofs48_out, nullptr);
+}
+
+int kzgmi_compute_blob_proofs_device(kzgmi_ctx* c, const kzgmi_blob_pk* pk, const void* d_blobs,
+                                     const void* d_commitments48, size_t nb, void* d_proofs48_out) {
+  return run_slot0(
+      c, [&] { return kzgmi_compute_blob_proofs_device_async(c, pk, 0, d_blobs, d_commitments48, nb, d_proofs48_out); });
+}
+
+int kzgmi_compute_blob_proofs(kzgmi_ctx* c, const kzgmi_blob_pk* pk, const uint8_t* blobs, const uint8_t* commitments48,
+                              size_t nb, uint8_t* proofs48_out) {
+  return blob_job_host(c, pk, BlobOp::BlobProofs, blobs, commitments48, nb, proofs48_out, nullptr);
+}
+
+int kzgmi_blob_quotient_device(kzgmi_ctx* c, const void* d_blobs, const void* d_zs, size_t nb, void* d_ys_out,
+                               void* d_q_out) {
+  CHK(check_ctx(c));
+  if (nb > kRecoverMaxBlobs) return fail(KZGMI_ERR_ARG, "too many blobs (max 4096 per call)");
+  if (nb && (!d_blobs || !d_zs || !d_ys_out || !d_q_out)) return fail(KZGMI_ERR_ARG, "null argument");
+  if (nb == 0) return 0;
+  if (((uintptr_t)d_blobs | (uintptr_t)d_zs | (uintptr_t)d_ys_out | (uintptr_t)d_q_out) & 15)
+    return fail(KZGMI_ERR_ARG, "device arrays must be 16-byte aligned");
+  return blob_slot0_job(c, [&](Slot& s, uint32_t* err) -> int {
+    BlobProofLaunch::quotient(s.stream, (const uint8_t*)d_blobs, (const uint8_t*)d_zs, c->blob_table.p, (uint32_t)nb, true,
+                              (uint8_t*)d_ys_out, (uint8_t*)d_q_out, err);
     return 0;
   });
 }

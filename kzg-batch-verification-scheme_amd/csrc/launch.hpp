@@ -201,6 +201,26 @@ struct Fk20Launch {
   static void emit(hipStream_t st, const void* in, size_t bytes, const uint32_t* err, void* out);
 };
 
+// ---- EIP-4844 commitments and proofs (blobproof.hpp, launch_blobproof.hip): BLS12-381 only
+struct BlobProofLaunch {
+  using XY = Xyzz<Bls12_381>;
+  using AF = Affine<Bls12_381>;
+  static constexpr uint32_t POINTS = 4096;          // the key: [L_j(tau)]_1, j < 4096
+  static constexpr uint32_t PARTS = 64;             // partial sums per blob: one per 64 bases
+  static size_t table_bytes();                      // the key's window table (affine rows)
+  static size_t table_flags();                      // its infinity flags: one byte per base
+  // the validated points -> table, tab_inf
+  static void key(hipStream_t st, const AF* pts, const uint8_t* inf, void* table, uint8_t* tab_inf);
+  // y_i = p_i(z_i) -> ys (nb x 32 B) and the quotient's evaluations q_i -> q (nb x 128 KiB, blob layout);
+  // domain: BlobLaunch's table; range_check: the blob elements are checked here (else they were already)
+  static void quotient(hipStream_t st, const uint8_t* blobs, const uint8_t* zs, const void* domain, uint32_t nb,
+                       bool range_check, uint8_t* ys, uint8_t* q, uint32_t* err);
+  // out[i] = sum_j scal[i][j] L_j for nb vectors of 4096 x 32 B big-endian scalars (q, or blobs);
+  // parts: nb * PARTS records of scratch; range_check: a scalar >= r raises DERR_SCALAR
+  static void msm(hipStream_t st, const uint8_t* scal, uint32_t nb, bool range_check, const void* table,
+                  const uint8_t* tab_inf, XY* parts, XY* out, uint32_t* err);
+};
+
 inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 }  // namespace kzgmi

@@ -102,6 +102,19 @@ def lib():
         "kzgmi_verify_blob_batch": ([vp, vp, vp, vp, vp, sz, ip], c.c_int),
         "kzgmi_verify_blob_batch_device": ([vp, vp, vp, vp, vp, sz, ip], c.c_int),
         "kzgmi_verify_blob_batch_device_async": ([vp, vp, c.c_int, vp, vp, vp, sz], c.c_int),
+        "kzgmi_blob_pk_load": ([vp, u8p, c.POINTER(vp)], c.c_int),
+        "kzgmi_blob_pk_free": ([vp], None),
+        "kzgmi_blob_pk_device_bytes": ([vp], sz),
+        "kzgmi_blob_commit": ([vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_blob_commit_device": ([vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_blob_commit_device_async": ([vp, vp, c.c_int, vp, sz, vp], c.c_int),
+        "kzgmi_compute_kzg_proofs": ([vp, vp, vp, vp, sz, vp, vp], c.c_int),
+        "kzgmi_compute_kzg_proofs_device": ([vp, vp, vp, vp, sz, vp, vp], c.c_int),
+        "kzgmi_compute_kzg_proofs_device_async": ([vp, vp, c.c_int, vp, vp, sz, vp, vp], c.c_int),
+        "kzgmi_compute_blob_proofs": ([vp, vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_compute_blob_proofs_device": ([vp, vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_compute_blob_proofs_device_async": ([vp, vp, c.c_int, vp, vp, sz, vp], c.c_int),
+        "kzgmi_blob_quotient_device": ([vp, vp, vp, sz, vp, vp], c.c_int),
         "kzgmi_cell_srs_load": ([vp, u8p, u8p, u8p, c.POINTER(vp)], c.c_int),
         "kzgmi_cell_srs_free": ([vp], None),
         "kzgmi_cell_batch_challenge_device": ([vp, vp, sz, vp, vp, vp, vp, sz, u8p], c.c_int),
@@ -195,6 +208,11 @@ def exported_symbols():
         "kzgmi_compute_cells_and_proofs_device_async", "kzgmi_recover_cells_and_proofs",
         "kzgmi_recover_cells_and_proofs_device", "kzgmi_recover_cells_and_proofs_device_async",
         "kzgmi_fk20_scalars_device", "kzgmi_g1_fft128_device",
+        "kzgmi_blob_pk_load", "kzgmi_blob_pk_free", "kzgmi_blob_pk_device_bytes",
+        "kzgmi_blob_commit", "kzgmi_blob_commit_device", "kzgmi_blob_commit_device_async",
+        "kzgmi_compute_kzg_proofs", "kzgmi_compute_kzg_proofs_device", "kzgmi_compute_kzg_proofs_device_async",
+        "kzgmi_compute_blob_proofs", "kzgmi_compute_blob_proofs_device", "kzgmi_compute_blob_proofs_device_async",
+        "kzgmi_blob_quotient_device",
     ]
 
 
@@ -412,6 +430,26 @@ class CellProofKey:
         try:
             if self.handle:
                 lib().kzgmi_cell_pk_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+@dataclass
+class BlobProofKey:
+    """EIP-4844 blob proof key: the 4096 Lagrange points [l_j(tau)]_1 (bit-reversed order) as a fixed-base
+    window table on the device (kzgmi_blob_pk_load)."""
+    ctx: "Context"
+    handle: ctypes.c_void_p
+
+    @property
+    def device_bytes(self) -> int:
+        return int(lib().kzgmi_blob_pk_device_bytes(self.handle)) if self.handle else 0
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().kzgmi_blob_pk_free(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -758,6 +796,100 @@ class Context:
         ptrs = (_dptr(blobs, n * BLOB_BYTES), _dptr(commitments, 48 * n), _dptr(proofs, 48 * n))
         self._order(slot)
         _check(lib().kzgmi_verify_blob_batch_device_async(self.handle, srs.handle, int(slot), *ptrs, int(n)))
+
+    # ------------------------------------------------------------------ EIP-4844 commitments and proofs
+    def load_blob_proof_key(self, g1_lagrange: bytes) -> BlobProofKey:
+        """The blob proof key of g1_lagrange = [l_j(tau)]_1 for the Lagrange polynomial of dom[j], j < 4096
+        (4096 x 96 B: the trusted setup's Lagrange points in bit-reversed order)."""
+        if len(g1_lagrange) != 4096 * 96:
+            raise ValueError("g1_lagrange must hold 4096 uncompressed G1 points (393216 bytes)")
+        h = ctypes.c_void_p()
+        _check(lib().kzgmi_blob_pk_load(self.handle, bytes(g1_lagrange), ctypes.byref(h)))
+        return BlobProofKey(self, h)
+
+    @staticmethod
+    def _blob_pk_handle(pk):
+        if not isinstance(pk, BlobProofKey):
+            raise KzgmiError(-1, "not a blob proof key (Context.load_blob_proof_key)")
+        return pk.handle
+
+    def _blob_job(self, name, pk, blobs, second, second_bytes, n, outs, out_bytes):
+        """One of the three producer calls: `second` (zs or commitments, second_bytes each; None for a
+        commitment), outputs of out_bytes[i] per blob.  Device tensors in: device tensors out (`outs[i]`
+        where given); host buffers in: bytes out."""
+        h = self._blob_pk_handle(pk)
+        ins = [blobs] + ([second] if second_bytes else [])
+        in_bytes = [BLOB_BYTES] + ([second_bytes] if second_bytes else [])
+        if _is_device_tensor(blobs):
+            import torch
+            if n is None:
+                n = blobs.numel() * blobs.element_size() // BLOB_BYTES
+            outs = [torch.empty(n * b, dtype=torch.uint8, device=blobs.device) if o is None else o
+                    for o, b in zip(outs, out_bytes)]
+            ptrs = [_dptr(x, n * b) for x, b in zip(ins, in_bytes)]
+            optrs = [_dptr(o, n * b) for o, b in zip(outs, out_bytes)]
+            self._order(0)
+            _check(getattr(lib(), name + "_device")(self.handle, h, *ptrs, int(n), *optrs))
+            return outs
+        held = [_host_ptr(x) for x in ins]
+        if n is None:
+            n = held[0][1] // BLOB_BYTES
+        if any(l < n * b for (_, l, _), b in zip(held, in_bytes)):
+            raise ValueError("input buffers shorter than n blobs")
+        bufs = [ctypes.create_string_buffer(max(1, n * b)) for b in out_bytes]
+        _check(getattr(lib(), name)(self.handle, h, *[p for p, _, _ in held], int(n),
+                                    *[ctypes.addressof(b) for b in bufs]))
+        del held
+        return [buf.raw[:n * b] for buf, b in zip(bufs, out_bytes)]
+
+    def _blob_job_async(self, name, pk, slot, blobs, second, second_bytes, n, outs, out_bytes):
+        h = self._blob_pk_handle(pk)
+        ptrs = [_dptr(blobs, n * BLOB_BYTES)] + ([_dptr(second, n * second_bytes)] if second_bytes else [])
+        optrs = [_dptr(o, n * b) for o, b in zip(outs, out_bytes)]
+        self._order(slot)
+        _check(getattr(lib(), name + "_device_async")(self.handle, h, int(slot), *ptrs, int(n), *optrs))
+
+    def blob_commit(self, pk: BlobProofKey, blobs, n: Optional[int] = None, out=None):
+        """blob_to_kzg_commitment for n blobs (n x 128 KiB): n x 48 B compressed commitments.  Device
+        tensor in: a device tensor out (`out` if given); host buffer in: bytes out."""
+        return self._blob_job("kzgmi_blob_commit", pk, blobs, None, 0, n, [out], [48])[0]
+
+    def blob_commit_async(self, pk: BlobProofKey, slot: int, blobs, n: int, out):
+        """Enqueue blob_commit of device tensors on `slot`; wait(slot) completes it (and raises its
+        device-side errors)."""
+        self._blob_job_async("kzgmi_blob_commit", pk, slot, blobs, None, 0, n, [out], [48])
+
+    def compute_kzg_proofs(self, pk: BlobProofKey, blobs, zs, n: Optional[int] = None, out=None, ys_out=None):
+        """compute_kzg_proof for n blobs at zs (n x 32 B big-endian, any z < r): (proofs, ys), n x 48 B
+        compressed proofs and n x 32 B evaluations y_i = p_i(z_i)."""
+        return tuple(self._blob_job("kzgmi_compute_kzg_proofs", pk, blobs, zs, 32, n, [out, ys_out], [48, 32]))
+
+    def compute_kzg_proofs_async(self, pk: BlobProofKey, slot: int, blobs, zs, n: int, out, ys_out):
+        """Enqueue compute_kzg_proofs of device tensors on `slot`; wait(slot) completes it."""
+        self._blob_job_async("kzgmi_compute_kzg_proofs", pk, slot, blobs, zs, 32, n, [out, ys_out], [48, 32])
+
+    def compute_blob_proofs(self, pk: BlobProofKey, blobs, commitments, n: Optional[int] = None, out=None):
+        """compute_blob_kzg_proof for n blobs and their compressed commitments (n x 48 B, validated): the
+        n x 48 B proofs at each blob's own challenge, as verify_blob_batch checks them."""
+        return self._blob_job("kzgmi_compute_blob_proofs", pk, blobs, commitments, 48, n, [out], [48])[0]
+
+    def compute_blob_proofs_async(self, pk: BlobProofKey, slot: int, blobs, commitments, n: int, out):
+        """Enqueue compute_blob_proofs of device tensors on `slot`; wait(slot) completes it."""
+        self._blob_job_async("kzgmi_compute_blob_proofs", pk, slot, blobs, commitments, 48, n, [out], [48])
+
+    def blob_quotient(self, blobs, zs, n: int, ys_out=None, out=None):
+        """Diagnostic: (ys, q) of n device-resident blobs at zs: y_i = p_i(z_i) (n x 32 B) and the
+        evaluations of (p_i - y_i) / (X - z_i) on the domain (n x 128 KiB, blob layout)."""
+        import torch
+        if ys_out is None:
+            ys_out = torch.empty(32 * n, dtype=torch.uint8, device=blobs.device)
+        if out is None:
+            out = torch.empty(n * BLOB_BYTES, dtype=torch.uint8, device=blobs.device)
+        ptrs = (_dptr(blobs, n * BLOB_BYTES), _dptr(zs, 32 * n))
+        py, pq = _dptr(ys_out, 32 * n), _dptr(out, n * BLOB_BYTES)
+        self._order(0)
+        _check(lib().kzgmi_blob_quotient_device(self.handle, *ptrs, int(n), py, pq))
+        return ys_out, out
 
     # ------------------------------------------------------------------ EIP-7594 cells
     def load_cell_srs(self, g1_monomial: bytes, g2: bytes, tau64_g2: bytes) -> CellSrs:
@@ -1300,6 +1432,21 @@ def recover_cells(cell_indices, cells, n_blobs: Optional[int] = None, ctx: Optio
     """The cells of EIP-7594 recover_cells_and_kzg_proofs on the GPU for blobs that share their cell
     indices (Context.recover_cells)."""
     return (ctx or default_context()).recover_cells(cell_indices, cells, n_blobs)
+
+
+def blob_commit(pk: BlobProofKey, blobs, n: Optional[int] = None):
+    """Context.blob_commit on the key's context."""
+    return pk.ctx.blob_commit(pk, blobs, n)
+
+
+def compute_kzg_proofs(pk: BlobProofKey, blobs, zs, n: Optional[int] = None):
+    """Context.compute_kzg_proofs on the key's context."""
+    return pk.ctx.compute_kzg_proofs(pk, blobs, zs, n)
+
+
+def compute_blob_proofs(pk: BlobProofKey, blobs, commitments, n: Optional[int] = None):
+    """Context.compute_blob_proofs on the key's context."""
+    return pk.ctx.compute_blob_proofs(pk, blobs, commitments, n)
 
 
 def compute_cells_and_proofs(pk: CellProofKey, blobs, n: Optional[int] = None, cells=True):
