@@ -68,7 +68,9 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * and recovery entry points kzgmi_compute_cells* and kzgmi_recover_cells*, and the cell proof entry
  * points kzgmi_cell_pk_*, kzgmi_*_cells_and_proofs*, kzgmi_fk20_scalars_device, kzgmi_g1_fft128_device,
  * and the EIP-4844 producer entry points kzgmi_blob_pk_*, kzgmi_blob_commit*, kzgmi_compute_kzg_proofs*,
- * kzgmi_compute_blob_proofs*, kzgmi_blob_quotient_device.
+ * kzgmi_compute_blob_proofs*, kzgmi_blob_quotient_device, and the search entry points
+ * kzgmi_batch_check_partials_device, kzgmi_batch_range_partials_device, kzgmi_batch_find_invalid*,
+ * kzgmi_verify_blob_batch_find_invalid*, kzgmi_find_invalid_stats.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -563,6 +565,60 @@ int kzgmi_msm_partial_device_async(kzgmi_ctx* ctx, kzgmi_curve curve, int slot, 
                                    const void* d_scalars, size_t n, void* d_partial_out);
 int kzgmi_msm_combine_device_async(kzgmi_ctx* ctx, kzgmi_curve curve, int slot,
                                    const void* d_partials, int n_parts);
+
+/* ---- locating the invalid tuples of a rejected batch -----------------------
+ * A verify call answers one bit for the whole batch.  These calls say WHICH tuples are wrong, by
+ * group testing over index ranges on the device: a range [lo, hi) passes iff
+ * e(A, [tau]_2) e(-B, [1]_2) = 1 for A = sum r_i pi_i, B = sum r_i C_i + (r_i z_i) pi_i - (r_i y_i) G1
+ * over its tuples, r_i the 127-bit counter-mode randomiser of the GLOBAL index i (as for shards);
+ * a failing range is split and its parts are tested, down to single tuples.  The search always uses
+ * counter-mode randomisers (seed32, or the OS CSPRNG when NULL), whatever mode produced the
+ * rejection: KZGMI_FLAG_POWERS and KZGMI_FLAG_FIAT_SHAMIR are KZGMI_ERR_ARG here; the flags taken
+ * are KZGMI_FLAG_COMPRESSED, KZGMI_FLAG_SUBGROUP_CHECK and KZGMI_FLAG_TRUSTED_G1.  All of them are
+ * synchronous, run on slot 0 (which must be idle) of the context's primary device, and report an
+ * input error (encoding, curve, subgroup, scalar >= r) as their return code with the outputs
+ * untouched: localising malformed encodings is out of scope.
+ *
+ * kzgmi_batch_check_partials_device: the verdict per record pair, ok_out[g] (0 / 1) for
+ * (A_g, B_g) = d_partials[2 g], [2 g + 1]; a marked record fails the call with its own code, as
+ * kzgmi_batch_combine_device does.  A sharded caller names the failing shard with it. */
+int kzgmi_batch_check_partials_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const void* d_partials,
+                                      size_t n_groups, uint8_t* ok_out);
+/* (A_g, B_g) of n_ranges index ranges (uint64 lo, hi pairs on the host, lo < hi <= n, any order,
+ * may overlap, n_ranges <= 65536) of one device-resident batch whose first tuple has global index
+ * index_offset; 2 records per range -> d_partials_out.  One wave per term in one launch (no
+ * buckets): meant for many short ranges; a call whose summation trees would pass the workspace
+ * bound (256 MiB: about 160 000 tuples over all ranges) is KZGMI_ERR_ARG. */
+int kzgmi_batch_range_partials_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const void* d_commitments,
+                                      const void* d_zs, const void* d_ys, const void* d_proofs, size_t n,
+                                      uint64_t index_offset, const uint8_t* seed32, uint32_t flags,
+                                      const uint64_t* ranges, size_t n_ranges, void* d_partials_out);
+/* bad_out: the lowest min(max_bad, #invalid) invalid indices, ascending; *n_bad_out their count;
+ * *more_out = 1 iff a further invalid tuple exists.  1 <= max_bad <= 4096.  n == 0: none.
+ * A tuple is invalid iff e(pi_i, [tau]_2) != e(C_i - y_i G1 + z_i pi_i, [1]_2).  Host arrays are
+ * staged like kzgmi_batch_verify_ex's. */
+int kzgmi_batch_find_invalid(kzgmi_ctx* ctx, const kzgmi_srs* srs, const uint8_t* commitments,
+                             const uint8_t* zs, const uint8_t* ys, const uint8_t* proofs, size_t n,
+                             const uint8_t* seed32, uint32_t flags, uint64_t* bad_out, size_t max_bad,
+                             size_t* n_bad_out, int* more_out);
+int kzgmi_batch_find_invalid_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const void* d_commitments,
+                                    const void* d_zs, const void* d_ys, const void* d_proofs, size_t n,
+                                    const uint8_t* seed32, uint32_t flags, uint64_t* bad_out,
+                                    size_t max_bad, size_t* n_bad_out, int* more_out);
+/* EIP-4844 blobs: z_i and y_i = p_i(z_i) by the blob stages, then the search on (C_i, z_i, y_i, pi_i)
+ * with KZGMI_FLAG_COMPRESSED | KZGMI_FLAG_SUBGROUP_CHECK semantics and verifier-private randomisers:
+ * the indices of the blobs kzgmi_verify_blob_batch rejects the batch for. */
+int kzgmi_verify_blob_batch_find_invalid(kzgmi_ctx* ctx, const kzgmi_srs* srs, const uint8_t* blobs,
+                                         const uint8_t* commitments48, const uint8_t* proofs48, size_t n,
+                                         uint64_t* bad_out, size_t max_bad, size_t* n_bad_out,
+                                         int* more_out);
+int kzgmi_verify_blob_batch_find_invalid_device(kzgmi_ctx* ctx, const kzgmi_srs* srs, const void* d_blobs,
+                                                const void* d_commitments48, const void* d_proofs48,
+                                                size_t n, uint64_t* bad_out, size_t max_bad,
+                                                size_t* n_bad_out, int* more_out);
+/* Of the last search on this context: levels, bucket partial jobs, wave-terms of the grouped kernel,
+ * pairings. */
+int kzgmi_find_invalid_stats(kzgmi_ctx* ctx, uint64_t out[4]);
 
 /* prover-side commitments with a fixed SRS base.  kzgmi_ck_load uploads
  * n G1 powers ([tau^i]_1, host encodings, validated) and precomputes 16 rows of 2^(16 w)-shifted

@@ -108,6 +108,9 @@ struct Slot {
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
   DevBuf acc29b, cntb, offb;                     // second bucket store of chunked batches (run_msm_core part)
+  // the search for invalid tuples (host_find.hip): a level's group table, -t_g, tree nodes and arrival
+  // counters (msm_group.hpp), its record pairs and their verdicts
+  DevBuf find_tab, find_negt, find_nodes, find_flags, find_rec, find_ok;
   // split accumulation (run_msm_core): the MSM of the first accumulation launch (MSM#0 by default,
   // MsmTuning::split_rev) reduces and combines on the context's one side stream beside the second
   // launch; side_ev[0] = the first launch's sets accumulated, [1] = its MSM combined
@@ -131,7 +134,8 @@ struct Slot {
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
                       &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z,
-                      &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc};
+                      &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc,
+                      &find_tab, &find_negt, &find_nodes, &find_flags, &find_rec, &find_ok};
     for (DevBuf* b : bufs) f(*b);
   }
 };
@@ -157,6 +161,8 @@ struct kzgmi_ctx {
   bool glv_batch = true;
   bool msm_trusted_g1 = false;
   MsmTuning tune;  // what plan_msm decides an MSM call by (msm_plan.hpp): the device's CUs and the KZGMI_* knobs
+  FindTuning find_tune;        // the search's fan-out, crossover and workspace bound (find_plan.hpp)
+  uint64_t find_stats[4] = {};  // of the last search: levels, bucket jobs, grouped wave-terms, pairings
   int host_chunks_env = 0;       // KZGMI_HOST_CHUNKS: ranges of a synchronous host-buffer batch (batch_host_chunked)
   int host_chunk_mode = 0;       // KZGMI_HOST_CHUNK_MODE=1: shard partials even where one bucket store applies
   // set by the synchronous device-buffer call while it enqueues: only such calls split (the first

@@ -5,6 +5,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "msm_small.hpp"
+#include "find_plan.hpp"
 
 namespace kzgmi {
 
@@ -98,9 +99,22 @@ struct Launch {
   // ---- pairing (launch_pairing.hip)
   static int num_lines();
   static void precompute_lines(hipStream_t st, const G2Aff<Cv>* q, Line<Cv>* lines);
-  static void pairing_check(hipStream_t st, const XY* res, const Line<Cv>* lines, const uint8_t* q_inf, int* ok);
+  // G record pairs (res[2 g], res[2 g + 1]) -> ok[g], one workgroup each
+  static void pairing_check(hipStream_t st, const XY* res, const Line<Cv>* lines, const uint8_t* q_inf, int* ok,
+                            uint32_t G = 1);
   static void pairing_one(hipStream_t st, const AF* p, const uint8_t* p_inf, const Line<Cv>* lines,
                           const uint8_t* q_inf, uint8_t* out);
+  // ---- grouped small MSMs (msm_group.hpp, launch_find.hip): the (A_g, B_g) of G index ranges of the resident
+  // batch of n tuples (points [pi | C | G1] in the radix-29 slots, scal_r, scal_s) -> res[2 g], res[2 g + 1].
+  // table: the G groups of find_group_plan (device); negt: G x 8 words of scratch, filled here from ys and
+  // the seed (global index = index_offset + position in the batch); flags (flag_words) are zeroed here
+  static void group_msm(hipStream_t st, const FindGroup* table, uint32_t G, uint32_t waves, uint32_t n,
+                        const Seed& seed, uint64_t index_offset, const uint8_t* ys, const uint32_t* scal_r,
+                        const uint32_t* scal_s, uint32_t* negt, const AF* pts, const uint8_t* inf, uint32_t* nodes,
+                        uint32_t* flags, size_t flag_words, XY* res);
+  // count records become marked when *err != 0; a marked record among them raises its code into *err
+  static void mark_records(hipStream_t st, XY* recs, uint32_t count, const uint32_t* err);
+  static void check_marks(hipStream_t st, const XY* recs, uint32_t count, uint32_t* err);
   // ---- prover commit key (launch_gen.hip): row out = 2^16 * row in, affine
   static void shift_points(hipStream_t st, const AF* in, const uint8_t* inf_in, uint32_t n, AF* out, uint8_t* inf_out);
   // ---- generators (launch_gen.hip)

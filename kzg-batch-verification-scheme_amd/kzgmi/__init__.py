@@ -166,6 +166,18 @@ def lib():
         "kzgmi_probe_fpmul": ([vp, c.c_int, c.POINTER(c.c_double)], c.c_int),
         "kzgmi_set_profiling": ([vp, c.c_int], c.c_int),
         "kzgmi_get_phase_ms": ([vp, c.POINTER(c.c_double), c.c_int], c.c_int),
+        "kzgmi_batch_check_partials_device": ([vp, vp, vp, sz, u8p], c.c_int),
+        "kzgmi_batch_range_partials_device": ([vp, vp, vp, vp, vp, vp, sz, c.c_uint64, u8p, c.c_uint32,
+                                               c.POINTER(c.c_uint64), sz, vp], c.c_int),
+        "kzgmi_batch_find_invalid": ([vp, vp, vp, vp, vp, vp, sz, u8p, c.c_uint32, c.POINTER(c.c_uint64), sz,
+                                      c.POINTER(sz), ip], c.c_int),
+        "kzgmi_batch_find_invalid_device": ([vp, vp, vp, vp, vp, vp, sz, u8p, c.c_uint32, c.POINTER(c.c_uint64), sz,
+                                             c.POINTER(sz), ip], c.c_int),
+        "kzgmi_verify_blob_batch_find_invalid": ([vp, vp, vp, vp, vp, sz, c.POINTER(c.c_uint64), sz, c.POINTER(sz), ip],
+                                                  c.c_int),
+        "kzgmi_verify_blob_batch_find_invalid_device": ([vp, vp, vp, vp, vp, sz, c.POINTER(c.c_uint64), sz,
+                                                         c.POINTER(sz), ip], c.c_int),
+        "kzgmi_find_invalid_stats": ([vp, c.POINTER(c.c_uint64)], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -213,6 +225,9 @@ def exported_symbols():
         "kzgmi_compute_kzg_proofs", "kzgmi_compute_kzg_proofs_device", "kzgmi_compute_kzg_proofs_device_async",
         "kzgmi_compute_blob_proofs", "kzgmi_compute_blob_proofs_device", "kzgmi_compute_blob_proofs_device_async",
         "kzgmi_blob_quotient_device",
+        "kzgmi_batch_check_partials_device", "kzgmi_batch_range_partials_device", "kzgmi_batch_find_invalid",
+        "kzgmi_batch_find_invalid_device", "kzgmi_verify_blob_batch_find_invalid",
+        "kzgmi_verify_blob_batch_find_invalid_device", "kzgmi_find_invalid_stats",
     ]
 
 
@@ -1256,6 +1271,90 @@ class Context:
         _check(lib().kzgmi_partial_encode_device(self.handle, CURVES[curve], p, int(count), out))
         return [out.raw[i * g1b:(i + 1) * g1b] for i in range(count)]
 
+    # ------------------------------------------------------------------ locating invalid tuples
+    def batch_check_partials(self, srs: Srs, partials, n_groups: int) -> list:
+        """The verdict of each of n_groups device-resident record pairs (A_g, B_g): a sharded caller
+        names its failing shard with it.  A marked record raises its own error."""
+        p = _dptr(partials, 2 * n_groups * self.partial_bytes(srs.curve))
+        out = ctypes.create_string_buffer(max(1, n_groups))
+        self._order(0)
+        _check(lib().kzgmi_batch_check_partials_device(self.handle, srs.handle, p, int(n_groups), out))
+        return [b != 0 for b in out.raw[:n_groups]]
+
+    def batch_range_partials(self, srs: Srs, commitments, zs, ys, proofs, n: int, index_offset: int, seed, ranges,
+                             out, compressed: bool = False, subgroup_check: bool = False, trusted_g1: bool = False):
+        """(A_g, B_g) of the index ranges [(lo, hi), ...] of a device-resident batch whose first tuple
+        has global index index_offset: 2 partial records per range into the device tensor `out`."""
+        flags = _flags(compressed, subgroup_check, trusted_g1=trusted_g1)
+        ptrs = self._batch_ptrs(srs.curve, commitments, zs, ys, proofs, n, compressed)
+        flat = [int(v) for r in ranges for v in r]
+        arr = (ctypes.c_uint64 * max(1, len(flat)))(*flat)
+        po = _dptr(out, 2 * len(ranges) * self.partial_bytes(srs.curve))
+        self._order(0)
+        _check(lib().kzgmi_batch_range_partials_device(self.handle, srs.handle, *ptrs, int(n), int(index_offset),
+                                                       _challenge_seed(seed, None), flags, arr, len(ranges), po))
+
+    @staticmethod
+    def _find_outputs(max_bad: int):
+        # (a max_bad outside 1 .. 4096 is the library's to refuse: it writes nothing then)
+        return (ctypes.c_uint64 * max(1, min(int(max_bad), 4096)))(), ctypes.c_size_t(0), ctypes.c_int(0)
+
+    def batch_find_invalid(self, srs: Srs, commitments, zs, ys, proofs, seed: Optional[bytes] = None,
+                           n: Optional[int] = None, max_bad: int = 64, compressed: bool = False,
+                           subgroup_check: bool = False, trusted_g1: bool = False, flags: Optional[int] = None):
+        """The invalid tuples of a batch, found on the GPU by group testing over index ranges:
+        -> (the lowest min(max_bad, #invalid) invalid indices ascending, more) with more True iff a
+        further invalid tuple exists.  Host buffers or device tensors, as batch_verify takes them.
+        The search uses counter-mode randomisers (seed, or the OS CSPRNG), whatever mode rejected
+        the batch.  flags: raw KZGMI_FLAG_* bits instead of the keywords."""
+        if flags is None:
+            flags = _flags(compressed, subgroup_check, trusted_g1=trusted_g1)
+        g1b = (1 if flags & FLAG_COMPRESSED else 2) * FP_BYTES[srs.curve]
+        bad, nb, more = self._find_outputs(max_bad)
+        sd = _challenge_seed(seed, None)
+        if _is_device_tensor(commitments):
+            if n is None:
+                n = commitments.numel() // g1b
+            ptrs = (_dptr(commitments, n * g1b), _dptr(zs, 32 * n), _dptr(ys, 32 * n), _dptr(proofs, n * g1b))
+            self._order(0)
+            _check(lib().kzgmi_batch_find_invalid_device(self.handle, srs.handle, *ptrs, int(n), sd, flags, bad,
+                                                         max_bad, ctypes.byref(nb), ctypes.byref(more)))
+        else:
+            ptrs, keep = self._host_inputs(commitments, zs, ys, proofs, n, g1b)
+            _check(lib().kzgmi_batch_find_invalid(self.handle, srs.handle, *ptrs[:4], int(ptrs[-1]), sd, flags, bad,
+                                                  max_bad, ctypes.byref(nb), ctypes.byref(more)))
+            del keep
+        return list(bad[:nb.value]), bool(more.value)
+
+    def blob_batch_find_invalid(self, srs: Srs, blobs, commitments, proofs, n: Optional[int] = None,
+                                max_bad: int = 64):
+        """The blobs verify_blob_batch rejects a batch for: -> (indices ascending, more).  Host buffers
+        or device tensors, as verify_blob_batch takes them."""
+        bad, nb, more = self._find_outputs(max_bad)
+        if _is_device_tensor(blobs):
+            if n is None:
+                n = commitments.numel() // 48
+            ptrs = (_dptr(blobs, n * BLOB_BYTES), _dptr(commitments, 48 * n), _dptr(proofs, 48 * n))
+            self._order(0)
+            _check(lib().kzgmi_verify_blob_batch_find_invalid_device(self.handle, srs.handle, *ptrs, int(n), bad,
+                                                                     max_bad, ctypes.byref(nb), ctypes.byref(more)))
+        else:
+            (pb, lb, kb), (pc, lc, kc), (pp, lp, kp) = (_host_ptr(v) for v in (blobs, commitments, proofs))
+            if n is None:
+                n = lc // 48
+            if lb < n * BLOB_BYTES or lc < 48 * n or lp < 48 * n:
+                raise ValueError("input buffers shorter than n blobs")
+            _check(lib().kzgmi_verify_blob_batch_find_invalid(self.handle, srs.handle, pb, pc, pp, int(n), bad, max_bad,
+                                                              ctypes.byref(nb), ctypes.byref(more)))
+            del kb, kc, kp
+        return list(bad[:nb.value]), bool(more.value)
+
+    def find_invalid_stats(self) -> dict:
+        """Of the last search on this context: levels, bucket_jobs, wave_terms (grouped kernel), pairings."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().kzgmi_find_invalid_stats(self.handle, out))
+        return dict(zip(("levels", "bucket_jobs", "wave_terms", "pairings"), list(out)))
+
     def batch_partial_async(self, srs: Srs, slot: int, commitments, zs, ys, proofs, n: int, index_offset: int,
                             seed, out, compressed: bool = False, subgroup_check: bool = False, challenge=None,
                             trusted_g1: bool = False):
@@ -1400,6 +1499,18 @@ def batch_verify(commitments, zs, ys, proofs, srs: Srs, seed: Optional[bytes] = 
 def verify_blob_batch(blobs, commitments, proofs, srs: Srs, n: Optional[int] = None) -> bool:
     """EIP-4844 verify_blob_kzg_proof_batch(blobs, commitments, proofs) on the GPU (BLS12-381)."""
     return srs.ctx.verify_blob_batch(srs, blobs, commitments, proofs, n=n)
+
+
+def batch_find_invalid(commitments, zs, ys, proofs, srs: Srs, seed: Optional[bytes] = None, max_bad: int = 64,
+                       compressed: bool = False, subgroup_check: bool = False, trusted_g1: bool = False):
+    """The invalid tuples of a rejected batch, found on the GPU: -> (indices ascending, more)."""
+    return srs.ctx.batch_find_invalid(srs, commitments, zs, ys, proofs, seed=seed, max_bad=max_bad,
+                                      compressed=compressed, subgroup_check=subgroup_check, trusted_g1=trusted_g1)
+
+
+def blob_batch_find_invalid(blobs, commitments, proofs, srs: Srs, n: Optional[int] = None, max_bad: int = 64):
+    """The blobs a rejected EIP-4844 blob batch is rejected for: -> (indices ascending, more)."""
+    return srs.ctx.blob_batch_find_invalid(srs, blobs, commitments, proofs, n=n, max_bad=max_bad)
 
 
 def verify_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs: CellSrs, r=None) -> bool:
