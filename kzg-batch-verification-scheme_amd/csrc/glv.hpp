@@ -11,7 +11,9 @@
 // Half-scalar format (what k_bin_count/k_bin_scatter read with scal_words = 4): |k_i| in
 // bits 0..126 of 4 LE words, bit 127 = "negative" (the term uses -P; msm.hpp folds it into
 // the entry's sign bit).  127-bit randomisers r_i have bit 127 clear, so both share a path.
-// Reference: none (LICENSE only); results are bit-identical to the unsplit MSM and checked
+// Reference: none (LICENSE only); glv_round_div and glv_split are held word for word to the exact
+// Babai rounding of oracle/pyspec/glv.py at the rounding and Barrett boundaries
+// (tests/test_gpu_points_ops.py), and MSM results are bit-identical to the unsplit MSM and checked
 // against the C oracle (tests/test_gpu_parity.py, test_gpu_glv.py).
 #pragma once
 #include "g1.hpp"

@@ -16,8 +16,6 @@
 // additions in Jacobian coordinates, one thread per point; beta is chosen in
 // tools/gen_params.py by checking the identity on the generator.
 #pragma once
-#include <type_traits>
-
 #include "field29.hpp"
 #include "kernels.hpp"
 
@@ -82,7 +80,12 @@ KZ_DEV Jac29 jac29_dbl(const Jac29& p) {
 // v == 0 mod p for any v < 2^12 p (one product by the Montgomery one brings it below 2p)
 KZ_DEV bool zero29(const G29& v) { return is_zero29(mul29(v, G29::from_const(Q29::ONE))); }
 
-// p + q, q affine (< 2p; madd-2007-bl).  p: X < 34p, Y < 18p, Z < 8p -> X3, Y3, Z3 < 8p
+// p + q, q affine (< 2p; madd-2007-bl).  p: X < 34p, Y < 18p, Z < 8p -> X3 < 8p, Y3, Z3 < 6p on the
+// general branch.  The exceptional branches only keep jac29_dbl's input contract (X < 34p, Y < 18p,
+// Z < 8p), which is all the chain needs (an addition's result goes to jac29_dbl): p = q returns
+// jac29_dbl(q), whose X3 = E^2 + 32p - 2D with D < 12p lies in [8p, 34p) (Y3 < 18p, Z3 < 4p); p = -q
+// returns p's own coordinates under the flag; p infinite returns (qx, qy, 1).  Checked case by case
+// in tests/test_gpu_points_ops.py (derivation in tests/pointref.py).
 __device__ __noinline__ Jac29 jac29_add_affine(const Jac29& p, const G29& qx, const G29& qy) {
   if (p.inf) return {qx, qy, G29::from_const(Q29::ONE), false};
   const G29 Z1Z1 = sqr29(p.z);
@@ -107,7 +110,10 @@ __device__ __noinline__ Jac29 jac29_add_affine(const Jac29& p, const G29& qx, co
   return r;
 }
 
-// p + q, both Jacobian (add-2007-bl); inputs as jac29_dbl's outputs -> X3 < 8p, Y3 < 6p, Z3 < 2p
+// p + q, both Jacobian (add-2007-bl); inputs as jac29_dbl's outputs -> X3 < 8p, Y3 < 6p, Z3 < 2p on
+// the general branch; p = q returns jac29_dbl(p) (X3 < 34p, Y3 < 18p, Z3 < 4p), p = -q returns p under
+// the flag and an infinite operand returns the other one: every result is inside jac29_dbl's outputs'
+// bounds, which is what its consumers (jac29_dbl, fp_from29 below 2^12 p) read under
 __device__ __noinline__ Jac29 jac29_add(const Jac29& p, const Jac29& q) {
   if (p.inf) return q;
   if (q.inf) return p;
@@ -290,95 +296,14 @@ __global__ void __launch_bounds__(256) k_compress_points(const uint8_t* __restri
 // the test is ~126 doublings, and a = 0 Jacobian doubling (dbl-2009-l, 2M + 5S = 7 products)
 // is cheaper than XYZZ doubling (6M + 3S = 9); the 10 additions cost a little more (madd
 // 7M + 4S, add 11M + 5S vs 8M + 2S, 12M + 2S): ~1020 instead of ~1255 products per point.
+// The chain itself runs in radix 2^29 (Jac29 above); this 32-bit form only holds its result for
+// the final comparison in k_subgroup_check.
 template <class Cv>
 struct Jac {
   using F = Fp<typename Cv::FpP>;
   F x, y, z;
   KZ_DEV bool is_inf() const { return z.is_zero(); }
 };
-
-template <class Cv>
-KZ_DEV Jac<Cv> jac_dbl(const Jac<Cv>& p) {
-  auto A = fp_sqr(p.x);
-  auto B = fp_sqr(p.y);
-  auto C = fp_sqr(B);
-  auto D = fp_dbl(fp_sub(fp_sub(fp_sqr(fp_add(p.x, B)), A), C));
-  auto E = fp_mul3(A);
-  auto Fv = fp_sqr(E);
-  Jac<Cv> r;
-  r.x = fp_sub(Fv, fp_dbl(D));
-  r.y = fp_sub(fp_mul(E, fp_sub(D, r.x)), fp_mul8(C));
-  r.z = fp_dbl(fp_mul(p.y, p.z));
-  return r;  // Z = 0 stays 0
-}
-
-// p + q, q affine (madd-2007-bl) with the exceptional cases
-template <class Cv>
-KZ_DEV Jac<Cv> jac_add_affine(const Jac<Cv>& p, const Affine<Cv>& q) {
-  using F = typename Jac<Cv>::F;
-  if (p.is_inf()) return {q.x, q.y, F::one()};
-  auto Z1Z1 = fp_sqr(p.z);
-  auto U2 = fp_mul(q.x, Z1Z1);
-  auto S2 = fp_mul(q.y, fp_mul(p.z, Z1Z1));
-  auto H = fp_sub(U2, p.x);
-  auto rr = fp_dbl(fp_sub(S2, p.y));
-  if (H.is_zero()) {
-    if (rr.is_zero()) return jac_dbl(Jac<Cv>{q.x, q.y, F::one()});
-    return {F::one(), F::one(), F::zero()};
-  }
-  auto HH = fp_sqr(H);
-  auto I = fp_mul4(HH);
-  auto J = fp_mul(H, I);
-  auto V = fp_mul(p.x, I);
-  Jac<Cv> r;
-  r.x = fp_sub(fp_sub(fp_sqr(rr), J), fp_dbl(V));
-  r.y = fp_sub(fp_mul(rr, fp_sub(V, r.x)), fp_dbl(fp_mul(p.y, J)));
-  r.z = fp_sub(fp_sub(fp_sqr(fp_add(p.z, H)), Z1Z1), HH);
-  return r;
-}
-
-// p + q, both Jacobian (add-2007-bl) with the exceptional cases
-template <class Cv>
-KZ_DEV Jac<Cv> jac_add(const Jac<Cv>& p, const Jac<Cv>& q) {
-  using F = typename Jac<Cv>::F;
-  if (p.is_inf()) return q;
-  if (q.is_inf()) return p;
-  auto Z1Z1 = fp_sqr(p.z);
-  auto Z2Z2 = fp_sqr(q.z);
-  auto U1 = fp_mul(p.x, Z2Z2);
-  auto U2 = fp_mul(q.x, Z1Z1);
-  auto S1 = fp_mul(p.y, fp_mul(q.z, Z2Z2));
-  auto S2 = fp_mul(q.y, fp_mul(p.z, Z1Z1));
-  auto H = fp_sub(U2, U1);
-  auto rr = fp_dbl(fp_sub(S2, S1));
-  if (H.is_zero()) {
-    if (rr.is_zero()) return jac_dbl(p);
-    return {F::one(), F::one(), F::zero()};
-  }
-  auto I = fp_sqr(fp_dbl(H));
-  auto J = fp_mul(H, I);
-  auto V = fp_mul(U1, I);
-  Jac<Cv> r;
-  r.x = fp_sub(fp_sub(fp_sqr(rr), J), fp_dbl(V));
-  r.y = fp_sub(fp_mul(rr, fp_sub(V, r.x)), fp_dbl(fp_mul(S1, J)));
-  r.z = fp_mul(fp_sub(fp_sub(fp_sqr(fp_add(p.z, q.z)), Z1Z1), Z2Z2), H);
-  return r;
-}
-
-// [|x|] q by the fixed bit pattern of the BLS parameter (uniform control flow)
-template <class Cv, class Base>
-KZ_DEV Jac<Cv> mul_by_x_abs(const Base& q, const Jac<Cv>& q_jac) {
-  constexpr uint64_t X = Cv::K::X_ABS;
-  Jac<Cv> acc = q_jac;  // top bit
-  for (int b = 62; b >= 0; --b) {
-    acc = jac_dbl(acc);
-    if ((X >> b) & 1) {
-      if constexpr (std::is_same_v<Base, Affine<Cv>>) acc = jac_add_affine(acc, q);
-      else acc = jac_add(acc, q);
-    }
-  }
-  return acc;
-}
 
 // Waves per SIMD the membership test is compiled for: 2 (256 VGPRs, no scratch in the doubling
 // loops) ran compressed batches at 22.5/s against 19.9 with the compiler's own choice (284

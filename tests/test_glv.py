@@ -5,8 +5,9 @@
 2. The product constants (csrc/params_gen.hpp, from tools/gen_params.py) equal the spec's.
 3. `device_split` restates csrc/glv.hpp step by step (Barrett rounding division, mod-2^128
    arithmetic, sign-magnitude halves) and must equal the spec's exact Babai rounding on
-   edge and random scalars.  The GPU kernel itself is checked through MSM parity
-   (tests/test_gpu_glv.py).
+   edge and random scalars.  The device code itself is held to the spec word for word by
+   tests/test_gpu_points_ops.py (glv.round_div_*, glv.split and the glv_split launcher), whose
+   cases tests/pointref.py picks with `device_round_div`'s count of Barrett corrections.
 """
 import os
 import random
@@ -33,23 +34,31 @@ def product_consts(curve):
     return out
 
 
+def device_round_div(curve, k, g, K=None):
+    """Mirror of glv.hpp glv_round_div: (round(k g / r), Barrett corrections taken)."""
+    r = pc.CURVES[curve].r
+    K = K or product_consts(curve)
+    N = k * g + K["GLV_HALF_R"]
+    q = ((N >> 224) * K["GLV_MU"]) >> 288
+    rem = (N - q * r) % (1 << 288)
+    steps = 0
+    for _ in range(2):
+        if rem >= r:
+            rem -= r
+            q += 1
+            steps += 1
+    assert rem < r, "Barrett needs more than two corrections"
+    assert q < 1 << 128
+    return q, steps
+
+
 def device_split(curve, k):
     """Mirror of glv.hpp glv_split: returns the two 128-bit sign-magnitude words."""
-    C = pc.CURVES[curve]
     K = product_consts(curve)
-    r, m128 = C.r, (1 << 128) - 1
+    m128 = (1 << 128) - 1
 
     def round_div(g):
-        N = k * g + K["GLV_HALF_R"]
-        q = ((N >> 224) * K["GLV_MU"]) >> 288
-        rem = (N - q * r) % (1 << 288)
-        for _ in range(2):
-            if rem >= r:
-                rem -= r
-                q += 1
-        assert rem < r, "Barrett needs more than two corrections"
-        assert q < 1 << 128
-        return q
+        return device_round_div(curve, k, g, K)[0]
 
     c1, c2 = round_div(K["GLV_G1"]), round_div(K["GLV_G2"])
     h0 = (k - c1 * K["GLV_A1"] - c2 * K["GLV_A2"]) & m128

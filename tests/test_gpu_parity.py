@@ -382,7 +382,7 @@ def test_accumulation_work_queue(curve, golden):
 @pytest.mark.parametrize("curve", CURVES)
 def test_msm_cancelling_buckets(pctx, curve):
     """Buckets whose running sum returns to infinity mid-chunk (P + (-P)), then keeps adding
-    (the accumulation's infinity flag, csrc/g1.hpp xyzz_acc_affine_lazy), doubling (P + P),
+    (the accumulation's infinity flag, csrc/msm.hpp acc_loop29), doubling (P + P),
     pieces that cancel across chunk boundaries (k_fixup), and an all-cancelling MSM (result
     infinity).  Equal scalars put every term of a window into one bucket."""
     C = pc.CURVES[curve]
