@@ -308,6 +308,7 @@ int kzgmi_ctx_create_device(kzgmi_ctx** out, int device_id, int pipeline_slots) 
   if (const char* e = getenv("KZGMI_HOST_CHUNKS")) c->host_chunks_env = std::max(1, atoi(e));
   if (const char* e = getenv("KZGMI_HOST_CHUNK_MODE")) c->host_chunk_mode = atoi(e);
   if (const char* e = getenv("KZGMI_SPLIT_ACC")) c->tune.split_acc = atoi(e) < 0 ? -1 : std::min(1, atoi(e));
+  if (const char* e = getenv("KZGMI_ACC_ROWS")) c->tune.acc_rows = atoi(e) < 0 ? -1 : std::min(1, atoi(e));
   if (const char* e = getenv("KZGMI_SPLIT_LOWPRIO")) c->tune.split_low_prio = atoi(e) != 0;
   if (const char* e = getenv("KZGMI_SEG4_WAVES")) c->tune.seg4_waves = std::max(0, atoi(e));
   if (const char* e = getenv("KZGMI_SPLIT_SIDEFIX")) c->tune.split_side_fix = atoi(e) != 0;

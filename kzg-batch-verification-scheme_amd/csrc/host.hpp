@@ -97,6 +97,7 @@ struct Slot {
   DevBuf acc29;                                  // radix-29 bucket records (msm.hpp)
   DevBuf accq;                                   // k_accumulate's work-queue counter (large calls)
   DevBuf crowd;                                  // k_fixup's list of crowded buckets (msm.hpp k_fixup_crowded)
+  DevBuf rowq, items, cuts;                      // row accumulation (msm.hpp): counters + histogram, item list, join list
   DevBuf fs_leaves, fs_tmp, fs_top, pow, chal;  // Fiat-Shamir / powers-of-r randomisers
   DevBuf blob_z, blob_y;                         // blob batches: the derived z_i, y_i (n x 32 B each);
                                                  // cell batches: z_k = h_k^64 and y_k = 0
@@ -131,7 +132,7 @@ struct Slot {
   template <class F>
   void for_each_buf(F&& f) {
     DevBuf* bufs[] = {&pts, &inf, &scal_r, &scal_s, &scal_t, &tpart, &cnt, &off, &coarse, &ent, &total, &sval, &skey,
-                      &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &fs_leaves,
+                      &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &rowq, &items, &cuts, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
                       &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z,
                       &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc,
@@ -169,6 +170,9 @@ struct kzgmi_ctx {
   // batch of a pipeline is alone when it is enqueued too, and split it cost the 20-step bench
   // ~1 ms: its two launches, then a gap while the next batch's front end ran)
   bool sync_call = false;
+  // set by the asynchronous device-buffer batch call while it enqueues: only such calls (and not
+  // the synchronous one, which enqueues through it) accumulate in rows (msm_plan.hpp MsmPlan::rows)
+  bool async_call = false;
   // accumulation order: a slot's k_accumulate waits for the accumulation D launches before it
   // (any slot), so at most D run at once and they start in submission order.  Without it 16
   // slots in flight ran their accumulations in bursts and their tails (pairing: one CU) together,

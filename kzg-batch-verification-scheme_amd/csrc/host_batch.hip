@@ -30,6 +30,11 @@ int kzgmi_batch_verify_device_ex_async(kzgmi_ctx* c, const kzgmi_srs* srs, int s
     return arm_empty(s, JobKind::Verdict);
   }
   Roctx rx("kzgmi_batch_verify_device_ex_async");
+  struct Guard {  // (kzgmi_ctx::async_call)
+    kzgmi_ctx* c;
+    explicit Guard(kzgmi_ctx* c_) : c(c_) { c->async_call = true; }
+    ~Guard() { c->async_call = false; }
+  } guard(c);
   return dispatch(srs->curve, [&](auto cv) -> int {
     return HostCore<decltype(cv)>::enqueue_batch(c, s, srs, dC, dz, dy, dpi, n, seed, 0, nullptr, flags);
   });

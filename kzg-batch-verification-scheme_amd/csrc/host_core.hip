@@ -37,6 +37,11 @@ static int ensure_msm(Slot& s, const MsmPlan& p) {
   CHK(s.total.ensure(z.total));
   if (p.acc_threads) CHK(s.accq.ensure(z.accq));
   CHK(s.crowd.ensure(z.crowd));
+  if (p.rows) {
+    CHK(s.rowq.ensure(z.rowq));
+    CHK(s.items.ensure(z.items));
+    CHK(s.cuts.ensure(z.cuts));
+  }
   CHK(s.sval.ensure(z.sval));
   CHK(s.skey.ensure(z.skey));
   CHK(s.acc29.ensure(z.acc29));
@@ -78,7 +83,8 @@ int HostCore<Cv>::run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uin
   // rows) are stored in that format already (kzgmi_ck_load)
   const bool own_pts = pts == nullptr && !pts29;
   const MsmTuning& t = c->tune;
-  const MsmPlan p = plan_msm<Cv>(t, tl_in, nsets, emax, mw, wbits, part, own_pts, slot_alone(c, s), c->sync_call);
+  const MsmPlan p = plan_msm<Cv>(t, tl_in, nsets, emax, mw, wbits, part, own_pts, slot_alone(c, s), c->sync_call,
+                                   c->async_call);
   CHK(ensure_msm(s, p));
   using XY = Xyzz<Cv>;
   using L = Launch<Cv>;
@@ -116,6 +122,11 @@ int HostCore<Cv>::run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uin
           (t.sort_split ? L::SORT_SPLIT : 0) | (t.sort_full_bins ? L::SORT_FULL_BINS : 0),
           p.second ? s.offb.template as<uint32_t>() : off, p.second ? s.cntb.template as<uint32_t>() : cnt, total, sval, skey,
           wbits);
+  // rows: the items of the sorted buckets, by length (in front of the ordering wait below: it runs
+  // beside the earlier batches' accumulations, like the sort)
+  if (p.rows)
+    L::row_items(st, off, cnt, NB, p.row_len, s.rowq.template as<uint32_t>(), s.items.template as<uint32_t>(),
+                 (uint32_t)p.row_items, s.cuts.template as<uint32_t>(), (uint32_t)p.row_cuts);
   mark(c, s, PH_SORT + 1);
   hipEvent_t* order_ev = nullptr;  // accumulation order (kzgmi_ctx::acc_order)
   const int order = emax >= kzgmi_ctx::ACC_ORDER_WIDE ? c->acc_order : c->acc_order_small;
@@ -182,6 +193,10 @@ int HostCore<Cv>::run_msm_core(kzgmi_ctx* c, Slot& s, const TermList& tl_in, uin
                   crowd, nullptr, st);
     if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));
     L::merge_buckets(st, NB, acc, cnt, accb, cntb);
+  } else if (p.rows) {
+    L::accumulate_rows(st, nchunks, sval, pts, acc, NB, s.rowq.template as<uint32_t>(), s.items.template as<uint32_t>(),
+                       (uint32_t)p.row_items, s.cuts.template as<uint32_t>(), (uint32_t)p.row_cuts);
+    if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));
   } else {
     L::accumulate(st, nchunks, total, sval, skey, off, cnt, pts, acc, NB, acc_threads, accq, crowd, nullptr, st);
     if (order_ev) HIPCHK(hipEventRecord(*order_ev, st));

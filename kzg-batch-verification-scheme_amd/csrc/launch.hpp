@@ -36,6 +36,17 @@ struct Launch {
   // nb: the record index of the launch's first piece (its pieces follow the nb bucket records)
   static void fixup(hipStream_t st, size_t nchunks, const uint32_t* total, const uint32_t* skey, const uint32_t* off,
                     const uint32_t* cnt, uint32_t* acc29, uint32_t nb, uint32_t* crowd, const uint32_t* lo);
+  // Row accumulation (msm.hpp k_accumulate_rows) of the whole sorted list.  row_items: the items
+  // of off / cnt (buckets of more than L entries cut), sorted by length, longest first, into
+  // `items` (3 x cap words) with the cut buckets' join list in `cuts` (cut_cap lines); rowq
+  // (RQ_WORDS words) is zeroed here and carries the counts to accumulate_rows, which walks the rows with `threads`
+  // threads (whole blocks of a resident round) and then joins the cut buckets' pieces (records
+  // nb + slot) into their records.  Both on st, row_items any time after the sort.
+  static void row_items(hipStream_t st, const uint32_t* off, const uint32_t* cnt, uint32_t nb, uint32_t L, uint32_t* rowq,
+                        uint32_t* items, uint32_t cap, uint32_t* cuts, uint32_t cut_cap);
+  static void accumulate_rows(hipStream_t st, size_t threads, const uint32_t* sval, const AF* pts, uint32_t* acc29,
+                              uint32_t nb, uint32_t* rowq, const uint32_t* items, uint32_t cap, const uint32_t* cuts,
+                              uint32_t cut_cap);
   static void pts_to29(hipStream_t st, AF* pts, uint32_t n);  // in place
   // acc29[b] += acc29b[b] for the buckets with cntb[b] != 0, cnt[b] += cntb[b] (chunked batches)
   static void merge_buckets(hipStream_t st, uint32_t nb, uint32_t* acc29, uint32_t* cnt, const uint32_t* acc29b,

@@ -82,6 +82,26 @@ void Launch<Cv>::fixup(hipStream_t st, size_t nchunks, const uint32_t* total, co
 }
 
 template <class Cv>
+void Launch<Cv>::row_items(hipStream_t st, const uint32_t* off, const uint32_t* cnt, uint32_t nb, uint32_t L, uint32_t* rowq,
+                           uint32_t* items, uint32_t cap, uint32_t* cuts, uint32_t cut_cap) {
+  (void)hipMemsetAsync(rowq, 0, (size_t)RQ_WORDS * 4, st);
+  const unsigned blocks = grid_for(nb, ITEMS_BLOCK);
+  k_items_hist<<<blocks, 256, 0, st>>>(cnt, nb, L, rowq);
+  k_items_scan<<<1, 256, 0, st>>>(L, rowq);
+  k_items_scatter<<<blocks, 256, 0, st>>>(off, cnt, nb, L, rowq, items, cap, cuts, cut_cap);
+}
+
+template <class Cv>
+void Launch<Cv>::accumulate_rows(hipStream_t st, size_t threads, const uint32_t* sval, const AF* pts, uint32_t* acc29,
+                                 uint32_t nb, uint32_t* rowq, const uint32_t* items, uint32_t cap, const uint32_t* cuts,
+                                 uint32_t cut_cap) {
+  k_accumulate_rows<Cv><<<grid_for(threads, 256), 256, 0, st>>>(rowq, items, cap, sval, pts, acc29);
+  // cut buckets: none at the sizes the planner picks rows for (a 2^20-tuple batch's largest bucket
+  // holds ~100 entries); the count is the device's, so a few waves look at it and leave
+  k_join_rows<Cv><<<64, 256, 0, st>>>(rowq, cuts, acc29, nb, cut_cap);
+}
+
+template <class Cv>
 void Launch<Cv>::pts_to29(hipStream_t st, AF* pts, uint32_t n) {
   if (n) k_pts_to29<Cv><<<grid_for(n, 256), 256, 0, st>>>(pts, n);
 }
@@ -140,6 +160,11 @@ template void Launch<KZ_CURVE_T>::accumulate(hipStream_t, size_t, const uint32_t
                                              uint32_t, size_t, uint32_t*, uint32_t*, const uint32_t*, hipStream_t);
 template void Launch<KZ_CURVE_T>::fixup(hipStream_t, size_t, const uint32_t*, const uint32_t*, const uint32_t*,
                                         const uint32_t*, uint32_t*, uint32_t, uint32_t*, const uint32_t*);
+template void Launch<KZ_CURVE_T>::row_items(hipStream_t, const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t*,
+                                            uint32_t*, uint32_t, uint32_t*, uint32_t);
+template void Launch<KZ_CURVE_T>::accumulate_rows(hipStream_t, size_t, const uint32_t*, const Affine<KZ_CURVE_T>*,
+                                                  uint32_t*, uint32_t, uint32_t*, const uint32_t*, uint32_t,
+                                                  const uint32_t*, uint32_t);
 template void Launch<KZ_CURVE_T>::pts_to29(hipStream_t, Affine<KZ_CURVE_T>*, uint32_t);
 template void Launch<KZ_CURVE_T>::reduce(hipStream_t, uint32_t, const uint32_t*, const uint32_t*, Xyzz<KZ_CURVE_T>*,
                                          Xyzz<KZ_CURVE_T>*, Xyzz<KZ_CURVE_T>*, Xyzz<KZ_CURVE_T>*, int, bool, int, int);

@@ -940,6 +940,11 @@ KZ_DEV F29<Q> one_literals(std::integer_sequence<int, K...>) {
 // p, x < 5.2p, y < 3.2p, zz, zzz < 1.1p with the biases 1p..8p.  Each subtraction names its
 // bias by role (Q::ACC_*), chosen and checked per curve by tools/gen_params29.py.  ZZ/ZZZ in
 // LDS as in the 32-bit loop below.
+// acc_row29 (row accumulation, below) holds a copy of this loop's helpers, value streaming and
+// addition body on another schedule -- a copy, so that this kernel's code generation is not
+// touched by it: a change to the addition is made at both sites (the stage test of the row path
+// compares the two kernels' records word for word).  Sharing the body is a follow-up that has to
+// clear an A/B of k_accumulate first.
 template <class Cv>
 KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t chunk, uint32_t cur,
                        const uint32_t* __restrict__ sorted_val, const uint32_t* __restrict__ sorted_key,
@@ -1259,6 +1264,278 @@ __global__ void __launch_bounds__(256) k_fixup_crowded(const uint32_t* __restric
     const uint32_t c1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)crowd[3 + 3 * i]);
     LpXyzz<Cv> acc = lp_load_x29(c, acc29 + ((size_t)nb + nthreads + c0) * W29);
     for (uint32_t cc = c0 + 1; cc <= c1; ++cc) acc = lp_xyzz_add(c, acc, lp_load_x29(c, acc29 + ((size_t)nb + cc) * W29));
+    lp_store_x29(c, acc29 + (size_t)key * W29, acc);
+  }
+}
+
+// ------------------------------------------------------------------------------ row accumulation
+// A second decomposition of the same sorted list (host_core.hip run_msm_core picks it for
+// pipelined BLS12-381 batches, msm_plan.hpp MsmPlan::rows): not equal chunks of entries but items.
+// An item is (record, first entry, length <= L): a bucket of cnt <= L entries is one item whose
+// record is the bucket's own, a larger bucket is cut into ceil(cnt / L) items whose records are
+// piece slots behind the nb bucket records, joined by k_join_rows.  The items are counting-sorted
+// by length, descending (k_items_hist -> k_items_scan -> k_items_scatter), and a wave walks a row
+// of 64 consecutive items in lockstep (k_accumulate_rows): every lane's first entry is the same
+// iteration, so the copy of a bucket's first point is a wave-uniform step with no addition
+// beside it (in k_accumulate the lane sits out an addition the other 63 run), nothing is flushed
+// inside the loop (there some lane changes bucket in 78 % of a wave's iterations and the whole
+// wave steps through the flush), and every lane stores its record once, after the row.  Rows
+// come from a counter, longest first.  Order inside a length class is whatever the atomics give:
+// an item is summed by one lane in entry order, so no record depends on it.
+constexpr uint32_t ROW_LEN_MAX = 256;  // largest item length L a plan may ask for (the LDS histograms)
+// words of the per-launch row queue `rowq`: the row counter, the item count, the cut buckets and
+// the piece slots handed out so far, then the length histogram and the scatter cursors
+enum : uint32_t {
+  RQ_NEXT = 0, RQ_NITEMS = 1, RQ_NCUT = 2, RQ_PIECES = 3, RQ_HIST = 4, RQ_CUR = RQ_HIST + ROW_LEN_MAX + 1,
+  RQ_WORDS = RQ_CUR + ROW_LEN_MAX + 1
+};
+
+// lengths of the items of a bucket of c entries, counted into h (c > 0): c / L items of length L
+// and one of c % L, or the bucket itself
+KZ_DEV void items_count(uint32_t* h, uint32_t c, uint32_t L) {
+  if (c <= L) {
+    atomicAdd(&h[c], 1u);
+  } else {
+    atomicAdd(&h[L], c / L);
+    if (c % L) atomicAdd(&h[c % L], 1u);
+  }
+}
+
+// Buckets per workgroup of the two passes over off / cnt: 256 threads x 4.  (One wave per SIMD, the
+// shape of every kernel that runs beside the accumulations: a 1024-thread workgroup needs a compute
+// unit with four free wave slots on every SIMD at once, which two accumulations in flight never leave.)
+constexpr uint32_t ITEMS_PER_THREAD = 4, ITEMS_BLOCK = 256 * ITEMS_PER_THREAD;
+
+// histogram of the item lengths 1..L (rowq zeroed before): privatised in LDS, one global atomic
+// per non-empty length and workgroup
+static __global__ void __launch_bounds__(256) k_items_hist(const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t L,
+                                                           uint32_t* __restrict__ rowq) {
+  __shared__ uint32_t h[ROW_LEN_MAX + 1];
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) h[t] = 0;
+  __syncthreads();
+#pragma unroll
+  for (uint32_t k = 0; k < ITEMS_PER_THREAD; ++k) {
+    const uint32_t b = blockIdx.x * ITEMS_BLOCK + k * 256 + threadIdx.x;
+    const uint32_t c = b < nb ? cnt[b] : 0u;
+    if (c) items_count(h, c, L);
+  }
+  __syncthreads();
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x)
+    if (h[t]) atomicAdd(&rowq[RQ_HIST + t], h[t]);
+}
+
+// one workgroup: where each length class starts in the descending list, and the item count
+static __global__ void __launch_bounds__(256) k_items_scan(uint32_t L, uint32_t* __restrict__ rowq) {
+  __shared__ uint32_t h[ROW_LEN_MAX + 1];
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) h[t] = t ? rowq[RQ_HIST + t] : 0u;
+  __syncthreads();
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) {
+    uint32_t before = 0;  // items longer than t
+    for (uint32_t l = t + 1; l <= L; ++l) before += h[l];
+    rowq[RQ_CUR + t] = before;
+    if (t == 0) rowq[RQ_NITEMS] = before;
+  }
+}
+
+// the item list, three arrays of `cap` words: record, first entry, length.  An uncut bucket ranks
+// inside its workgroup by the LDS atomic's return and the workgroup reserves its run of every
+// class with one global atomic; a cut bucket (rare) takes its piece slots, its line of the join
+// list `cuts` (key, first piece slot, pieces; cut_cap lines) and its items' ranks from global atomics.
+static __global__ void __launch_bounds__(256) k_items_scatter(const uint32_t* __restrict__ off,
+                                                              const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t L,
+                                                              uint32_t* __restrict__ rowq, uint32_t* __restrict__ items,
+                                                              uint32_t cap, uint32_t* __restrict__ cuts, uint32_t cut_cap) {
+  __shared__ uint32_t h[ROW_LEN_MAX + 1], base[ROW_LEN_MAX + 1];
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) h[t] = 0;
+  __syncthreads();
+  uint32_t c[ITEMS_PER_THREAD], rank[ITEMS_PER_THREAD];
+#pragma unroll
+  for (uint32_t k = 0; k < ITEMS_PER_THREAD; ++k) {
+    const uint32_t b = blockIdx.x * ITEMS_BLOCK + k * 256 + threadIdx.x;
+    c[k] = b < nb ? cnt[b] : 0u;
+    rank[k] = c[k] && c[k] <= L ? atomicAdd(&h[c[k]], 1u) : 0u;
+  }
+  __syncthreads();
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x)
+    if (h[t]) base[t] = atomicAdd(&rowq[RQ_CUR + t], h[t]);
+  __syncthreads();
+  auto put = [&](uint32_t pos, uint32_t rec, uint32_t first, uint32_t len) {
+    if (pos >= cap) return;  // never: cap bounds the items of any count array (msm_plan.hpp row_items)
+    items[pos] = rec;
+    items[cap + pos] = first;
+    items[2 * (size_t)cap + pos] = len;
+  };
+#pragma unroll
+  for (uint32_t k = 0; k < ITEMS_PER_THREAD; ++k) {
+    const uint32_t b = blockIdx.x * ITEMS_BLOCK + k * 256 + threadIdx.x;
+    if (!c[k]) continue;
+    const uint32_t o = off[b];
+    if (c[k] <= L) {
+      put(base[c[k]] + rank[k], b, o, c[k]);
+      continue;
+    }
+    const uint32_t np = (c[k] + L - 1) / L;
+    const uint32_t slot = atomicAdd(&rowq[RQ_PIECES], np);
+    const uint32_t line = atomicAdd(&rowq[RQ_NCUT], 1u);
+    if (line >= cut_cap) continue;  // never either: fewer than emax / L buckets are longer than L (row_cuts)
+    cuts[3 * (size_t)line] = b;
+    cuts[3 * (size_t)line + 1] = slot;
+    cuts[3 * (size_t)line + 2] = np;
+    for (uint32_t j = 0; j < np; ++j) {
+      const uint32_t len = min(L, c[k] - j * L);
+      put(atomicAdd(&rowq[RQ_CUR + len], 1u), nb + slot + j, o + j * L, len);
+    }
+  }
+}
+
+// One item: the sum of the entries [first, first + len) into record rec.  The mixed addition, its
+// biases and bounds, ZZ / ZZZ in the LDS columns and the value groups in LDS are those of
+// acc_loop29 above; what differs is the schedule.  The first entry is copied in front of the loop
+// (every live lane of the row at once), the loop body never flushes, and the one record is stored
+// behind it.  Values: the aligned 16-B group that holds the entry, as acc_loop29 reads them (an
+// item starts on any 4-B boundary; the lanes of a row then fetch their next group in different
+// iterations of four, a masked issue of one load each).
+// The lambdas, the value streaming and the addition body are copied from acc_loop29, not shared with
+// it (see the note there): keep the two in step.
+template <class Cv>
+KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t* __restrict__ sorted_val,
+                      const uint32_t* __restrict__ pts29, uint32_t* __restrict__ acc29) {
+  using Q = Fp29Of<Cv>;
+  using G = F29<Q>;
+  constexpr int N = Q::N, W29 = kW29<Q>;
+  __shared__ uint32_t s_zz[N][256], s_zzz[N][256];
+  __shared__ uint4 s_vq[256];
+  const uint32_t tx = threadIdx.x;
+  auto ld = [tx](uint32_t (&a)[N][256]) {
+    asm volatile("" ::: "memory");
+    G r;
+    _Pragma("unroll") for (int k = 0; k < N; ++k) r.v[k] = a[k][tx];
+    return r;
+  };
+  auto st = [tx](uint32_t (&a)[N][256], const G& v) {
+    _Pragma("unroll") for (int k = 0; k < N; ++k) a[k][tx] = v.v[k];
+    asm volatile("" ::: "memory");
+  };
+  auto put = [](uint32_t* d, const G& a) {
+    if constexpr (N % 2 == 0) {
+      _Pragma("unroll") for (int k = 0; k < N / 2; ++k) reinterpret_cast<uint2*>(d)[k] = make_uint2(a.v[2 * k], a.v[2 * k + 1]);
+    } else {
+      _Pragma("unroll") for (int k = 0; k < N; ++k) d[k] = a.v[k];
+    }
+  };
+  auto load_q = [&](uint32_t v, G& qx, G& qy) {
+    load_pt29<Cv>(reinterpret_cast<const Affine<Cv>*>(pts29) + sv_point(v), qx, qy);
+    if (v & 1) qy = sub29(G::zero(), qy, Q::ACC_NEG);
+  };
+  auto set_one = [&]() {  // ONE from literal moves (acc_loop29)
+    const G one = one_literals<Q>(std::make_integer_sequence<int, N / 2>{});
+    st(s_zz, one);
+    st(s_zzz, one);
+  };
+  uint4* const vq_wave = &s_vq[tx & ~63u];  // each lane's 16 B land at vq_wave[lane]
+  const uint32_t end = first + len;
+  uint32_t e = first;
+  G x, y;
+  bool inf = false;
+  // the item's first entry: running sum := its point
+  load_q(sorted_val[e], x, y);
+  set_one();
+  ++e;
+  for (;;) {
+    bool dbl = false;
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + (e & ~3u)), vq_wave, 16, 0, 0);
+    for (; e < end; ++e) {
+      const uint32_t j = e & 3u;
+      uint32_t lane;
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+      const uint32_t v = reinterpret_cast<const uint32_t*>(&s_vq[(tx & ~63u) + lane])[j];
+      if (j == 3) {
+        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): v is read before the next group lands over it
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + e + 1), vq_wave, 16, 0, 0);
+      }
+      G qx, qy;
+      load_q(v, qx, qy);
+      if (inf) {  // after P + (-P): this entry starts the sum again (rare, per lane)
+        x = qx;
+        y = qy;
+        set_one();
+        inf = false;
+        continue;
+      }
+      const G P = kFusedSub<Cv> ? mulsub29(qx, ld(s_zz), x, Q::ACC_P) : sub29(mul29(qx, ld(s_zz)), x, Q::ACC_P);
+      const G R = kFusedSub<Cv> ? mulsub29(qy, ld(s_zzz), y, Q::ACC_R) : sub29(mul29(qy, ld(s_zzz)), y, Q::ACC_R);
+      if (is_zero29_mf(P)) {
+        if (is_zero29_mf(R)) {
+          dbl = true;
+          break;
+        }
+        inf = true;
+        continue;
+      }
+      const G PP = sqr29(P);
+      const G PPP = mul29(P, PP);
+      st(s_zz, mul29(ld(s_zz), PP));
+      st(s_zzz, mul29(ld(s_zzz), PPP));
+      const G Q2 = mul29(x, PP);
+      const G X3 = kFusedSub<Cv> ? sqrsub3_29(R, PPP, Q2, Q::ACC_X3) : sub3_29(sqr29(R), PPP, Q2, Q::ACC_X3);
+      y = mul2_29(R, sub29(Q2, X3, Q::ACC_QX), y, neg_lazy29(PPP, Q::ACC_PPP));
+      x = X3;
+    }
+    if (!dbl) break;
+    G qx, qy;  // entry e: running sum := 2 q (out of the hot loop, as in acc_loop29)
+    load_q(sorted_val[e], qx, qy);
+    asm volatile("" ::: "memory");
+    const Xy29<Q> d = dbl_affine29<Q>(qx, qy, &s_zz[0][tx], &s_zzz[0][tx]);
+    asm volatile("" ::: "memory");
+    x = d.x;
+    y = d.y;
+    ++e;
+  }
+  uint32_t* d = acc29 + (size_t)rec * W29;
+  put(d, x);
+  put(d + N, y);
+  put(d + 2 * N, inf ? G::zero() : ld(s_zz));  // zz = 0 marks infinity
+  put(d + 3 * N, ld(s_zzz));
+}
+
+// the launch shape of k_accumulate (one resident round); every wave takes rows of 64 consecutive
+// items from the counter until the list is through
+template <class Cv>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAccWaves<Cv>))) k_accumulate_rows(
+    uint32_t* __restrict__ rowq, const uint32_t* __restrict__ items, uint32_t cap,
+    const uint32_t* __restrict__ sorted_val, const Affine<Cv>* __restrict__ pts, uint32_t* __restrict__ acc29) {
+  const uint32_t nitems = rowq[RQ_NITEMS];
+  const uint32_t lane = threadIdx.x & 63u;
+  for (;;) {
+    uint32_t row = 0;
+    if (lane == 0) row = atomicAdd(&rowq[RQ_NEXT], 1u);
+    row = __shfl(row, 0);
+    if ((uint64_t)row * 64 >= nitems) break;
+    const uint32_t i = row * 64 + lane;
+    if (i < nitems)
+      acc_row29<Cv>(items[cap + i], items[2 * (size_t)cap + i], items[i], sorted_val,
+                    reinterpret_cast<const uint32_t*>(pts), acc29);
+  }
+}
+
+// the cut buckets listed by k_items_scatter: one wave per bucket, its pieces (consecutive piece
+// slots, in entry order) added in lane-parallel arithmetic as k_fixup_crowded joins its pieces;
+// any grid (waves stride over the list, none when no bucket was cut)
+template <class Cv>
+__global__ void __launch_bounds__(256) k_join_rows(const uint32_t* __restrict__ rowq, const uint32_t* __restrict__ cuts,
+                                                   uint32_t* __restrict__ acc29, uint32_t nb, uint32_t cut_cap) {
+  KZ_TAIL_PRIO();
+  constexpr int W29 = kW29<Fp29Of<Cv>>;
+  const uint32_t n = min((uint32_t)__builtin_amdgcn_readfirstlane((int)rowq[RQ_NCUT]), cut_cap);  // (the lines written)
+  if (n == 0) return;
+  const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
+  const LpCtx<Cv> c = lp_ctx<Cv>();
+  for (uint32_t i = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64; i < n; i += nwaves) {
+    const uint32_t key = (uint32_t)__builtin_amdgcn_readfirstlane((int)cuts[3 * (size_t)i]);
+    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)cuts[3 * (size_t)i + 1]);
+    const uint32_t np = (uint32_t)__builtin_amdgcn_readfirstlane((int)cuts[3 * (size_t)i + 2]);
+    LpXyzz<Cv> acc = lp_load_x29(c, acc29 + ((size_t)nb + slot) * W29);
+    for (uint32_t j = 1; j < np; ++j) acc = lp_xyzz_add(c, acc, lp_load_x29(c, acc29 + ((size_t)nb + slot + j) * W29));
     lp_store_x29(c, acc29 + (size_t)key * W29, acc);
   }
 }

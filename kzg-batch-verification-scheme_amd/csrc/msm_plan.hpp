@@ -43,6 +43,12 @@ struct MsmTuning {
   // reduction segments on 4 threads instead of 2 while that grid stays within seg4_waves waves per
   // SIMD (Launch::reduce; KZGMI_SEG4_WAVES, 0: always 2)
   int seg4_waves = 1;
+  // Row accumulation (msm.hpp k_accumulate_rows) instead of the equal-chunk kernel: -1 the
+  // asynchronous BLS12-381 batches of at least ROWS_FROM entries, whose uneven queue tail the next
+  // batch's accumulation fills; 0 never; 1 every unsplit single-store call (KZGMI_ACC_ROWS; tests, A/B)
+  static constexpr size_t ROWS_FROM = size_t(1) << 23;
+  int acc_rows = -1;
+  uint32_t row_len = ROW_LEN_MAX;  // L: the longest item, a longer bucket is cut (no knob: the stage tests set 8)
 };
 
 // Window width of a call from its entry count at c = 16 (msm.hpp Win): c = 13 for mid-size calls,
@@ -137,6 +143,7 @@ struct MsmBytes {
   size_t small_nodes, small_flags;  // small form (with res); in a bucket plan only from plan_reserve
   size_t digits, cnt, off, cntb, offb, coarse, ent, total, accq, crowd, sval, skey, acc29, acc29b, R, U, scratch, winsum;
   size_t res;
+  size_t rowq, items, cuts;  // row accumulation: counters + histogram, the item list, the join list
 };
 
 struct MsmPlan {
@@ -156,6 +163,12 @@ struct MsmPlan {
   size_t pieces;       // bucket pieces the launches may flush (two records each, behind the NB buckets)
   size_t crowd_words;  // one list of crowded buckets (a split's second list follows the first)
   bool second;         // this range accumulates into the second store, then merges
+  // row accumulation (msm.hpp): the launch takes rows of 64 items, sorted by length, instead of chunks
+  bool rows;
+  uint32_t row_len;    // L: items are at most this long
+  size_t row_items;    // capacity of the item list (three arrays of it)
+  size_t row_pieces;   // piece slots of cut buckets: records NB + slot, handed out as buckets are cut
+  size_t row_cuts;     // lines of the join list (bucket, first piece slot, pieces)
   MsmBytes bytes;
 };
 
@@ -202,7 +215,7 @@ inline void plan_small(MsmPlan& p, const MsmWindows& mw) {
 // other slot of the context has a job in flight.  sync_call: a synchronous device-buffer call.
 template <class Cv>
 MsmPlan plan_msm(const MsmTuning& t, const TermList& tl_in, uint32_t nsets, size_t emax, const MsmWindows& mw, int wbits,
-                 int part, bool own_pts, bool alone, bool sync_call) {
+                 int part, bool own_pts, bool alone, bool sync_call, bool async_call = false) {
   using XY = Xyzz<Cv>;
   MsmPlan p{};
   TermList& tl = p.tl = tl_in;
@@ -267,6 +280,20 @@ MsmPlan plan_msm(const MsmTuning& t, const TermList& tl_in, uint32_t nsets, size
   p.pieces = p.can_split && t.split_side_fix ? 2 * nchunks : nchunks;
   p.crowd_words = 1 + 3 * (p.pieces / FIX_LP_FROM + 2);  // at most one per FIX_LP_FROM + 1 chunks
   p.second = part >= 2;
+  // Rows: only the unsplit static launch into the one store.  By default only asynchronous
+  // BLS12-381 batches of at least ROWS_FROM entries: a row queue ends unevenly (its last rows are
+  // the shortest, still tens of additions long), which the next batch's accumulation fills in a
+  // pipeline and nothing does in a lone call.
+  p.row_len = std::min<uint32_t>(std::max<uint32_t>(t.row_len, 1), ROW_LEN_MAX);
+  p.rows = part == 0 && !p.split && !p.acc_threads &&
+           (t.acc_rows > 0 || (t.acc_rows < 0 && Cv::ID == 0 && async_call && !sync_call && emax >= MsmTuning::ROWS_FROM));
+  if (p.rows) {
+    // a bucket of cnt > L entries is ceil(cnt / L) <= cnt / L + 1 items and fewer than emax / L
+    // buckets are that long: below 2 emax / L piece slots, and as many more items than buckets
+    p.row_cuts = emax / p.row_len + 1;
+    p.row_pieces = 2 * p.row_cuts;
+    p.row_items = ((size_t)p.NB + p.row_pieces + 63) / 64 * 64;
+  }
   constexpr size_t rec = (size_t)kW29<Fp29Of<Cv>> * 4;  // a radix-29 record: buckets, bucket pieces, R / U / V
   MsmBytes& z = p.bytes;
   z.digits = p.ndig * 4;
@@ -279,7 +306,12 @@ MsmPlan plan_msm(const MsmTuning& t, const TermList& tl_in, uint32_t nsets, size
   z.crowd = 4 * p.crowd_words * (p.can_split ? 2 : 1);
   z.sval = emax * 4 + 16;  // + 16: k_accumulate reads values 4 at a time, up to 3 past the end
   z.skey = emax * 4;
-  z.acc29 = ((size_t)p.NB + 2 * p.pieces) * rec;
+  z.acc29 = ((size_t)p.NB + std::max(2 * p.pieces, p.row_pieces)) * rec;  // (either path may run on a reserved slot)
+  if (p.rows) {
+    z.rowq = (size_t)RQ_WORDS * 4;
+    z.items = 3 * p.row_items * 4;
+    z.cuts = 3 * p.row_cuts * 4;
+  }
   if (p.second) z.acc29b = ((size_t)p.NB + 2 * nchunks) * rec;
   z.R = (size_t)p.NB / SEG * rec;
   z.U = (size_t)p.NB / SEG * rec * 2;  // U records, then the V records
@@ -305,7 +337,7 @@ MsmPlan plan_reserve(const MsmTuning& t, bool glv, bool powers, size_t n, bool o
   auto plan = [&](size_t nb) {
     const BatchTerms bt = terms(nb);
     return plan_msm<Cv>(t, bt.tl, bt.nsets, bt.emax, bt.mw, batch_wbits(t, powers, nb), 0, own_pts, /*alone=*/true,
-                        /*sync_call=*/false);
+                        /*sync_call=*/false, /*async_call=*/true);
   };
   // the largest batch of at most n tuples with ok(its terms): ok holds up to some size (0: for none)
   auto largest = [&](auto ok) {

@@ -23,7 +23,9 @@ for f in glob.glob(os.path.join(src, "**", "*counter_collection.csv"), recursive
 out = {"command": "tools/prof.sh sq: rocprofv3 --pmc <SQ counters> | FETCH_SIZE | WRITE_SIZE (separate passes, "
                   "--kernel-include-regex) -- python3 tools/phase_timing.py --reps 2 (n = %d %s, single batches)" % (n, CV),
        "per_launch": {k: {c: sum(v) / len(v) for c, v in cs.items()} for k, cs in per.items()}}
-acc = out["per_launch"].get("kzgmi::k_accumulate<kzgmi::%s>" % CV)
+# the accumulation kernel the run took: the equal-chunk one, or the row kernel (KZGMI_ACC_ROWS=1)
+acc = out["per_launch"].get("kzgmi::k_accumulate<kzgmi::%s>" % CV) or out["per_launch"].get(
+    "kzgmi::k_accumulate_rows<kzgmi::%s>" % CV)
 if acc and "SQ_INSTS_VALU" in acc:
     wc = acc["SQ_WAVE_CYCLES"]
     out["k_accumulate"] = {

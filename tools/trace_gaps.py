@@ -19,7 +19,8 @@ import sys
 
 def short(name):
     n = name.split("(")[0].replace("void ", "").replace("kzgmi::", "")
-    return n.split("<")[0]
+    n = n.split("<")[0]
+    return "k_accumulate" if n == "k_accumulate_rows" else n  # either accumulation kernel (msm.hpp)
 
 
 def main(path):

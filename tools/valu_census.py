@@ -4,6 +4,7 @@
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I kzg-batch-verification-scheme_amd/csrc \
         -DKZ_CURVE=0 -S --cuda-device-only kzg-batch-verification-scheme_amd/csrc/launch_msm.hip -o /tmp/lm0.s
     python tools/valu_census.py /tmp/lm0.s bls12_381 [mix_rate.txt]
+    python tools/valu_census.py /tmp/lm0.s bls12_381+rows [mix_rate.txt]    (k_accumulate_rows)
 
 The loop body of one mixed addition is straight-line code in a few basic blocks: the point load
 and conditional negation, then the two blocks holding the products (the blocks with >= 300
@@ -63,7 +64,11 @@ def category(op):
 def main():
     path, curve = sys.argv[1], sys.argv[2]
     mix = sys.argv[3] if len(sys.argv) > 3 else None
+    rows = curve.endswith("+rows")  # bls12_381+rows: the row kernel's loop (msm.hpp k_accumulate_rows)
+    curve = curve[:-5] if rows else curve
     sym = {"bls12_381": "_ZN5kzgmi12k_accumulateINS_9Bls12_381", "bn254": "_ZN5kzgmi12k_accumulateINS_5Bn254"}[curve]
+    if rows:
+        sym = sym.replace("12k_accumulate", "17k_accumulate_rows")
     n_limbs = 14 if curve == "bls12_381" else 9
     bl = blocks(path, sym)
     # the first copy of the loop: the blocks with >= 300 mads, and the negation block before them
@@ -82,8 +87,9 @@ def main():
     cats["column"] += col_and
     cats["carry"] -= col_and
     valu = sum(k for op, k in ops.items() if op.startswith("v_"))
-    print("k_accumulate<%s> hot loop, blocks %s (static-grid copy): %d instructions, %d VALU"
-          % (curve, ", ".join(bl[i][0] for i in idx), sum(ops.values()), valu))
+    print("%s<%s> hot loop, blocks %s (%s): %d instructions, %d VALU"
+          % ("k_accumulate_rows" if rows else "k_accumulate", curve, ", ".join(bl[i][0] for i in idx), "its one copy" if rows else "static-grid copy",
+             sum(ops.values()), valu))
     print("  Montgomery reductions in the loop: %.1f (v_mul_lo_u32 / %d limbs)" % (nprod, n_limbs))
     for c in ("mad", "column", "carry", "zero_test", "lane_lds", "s_nop"):
         print("  %-10s %5d" % (c, cats[c]))
