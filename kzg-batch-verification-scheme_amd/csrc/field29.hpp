@@ -313,11 +313,31 @@ KZ_DEV F29<Q> sub3_29(const F29<Q>& a, const F29<Q>& s, const F29<Q>& t, const u
 
 // B - b limb by limb, no carry pass (B biased, b normalised): limbs in (0, 2^30), NOT normalised.
 // Only as one operand of a product whose column sums keep their headroom -- in the accumulation,
-// the y PPP pair of mul2_29: 14 x 2^59 + (14 + 14) x 2^58 < 2^64 (BLS12-381; BN254 9 limbs)
+// the y PPP pair of mul2_29: 14 x 2^59 + (14 + 14) x 2^58 < 2^64 (BLS12-381; BN254 9 limbs), and
+// in the row loop the negated q.y of R = q.y ZZZ - y: 14 x 2^59 + 14 x 2^58 + a 2^30 addend.  The
+// product scan returns the words of the integer, whatever limbs carried it in.
 template <class Q>
 KZ_DEV F29<Q> neg_lazy29(const F29<Q>& b, const uint32_t (&B)[Q::N]) {
   F29<Q> r;
   _Pragma("unroll") for (int i = 0; i < Q::N; ++i) r.v[i] = B[i] - b.v[i];
+  return r;
+}
+
+// the carry pass on its own (limbs below 2^31 in): the same integer, normalised.  On
+// neg_lazy29(b, B) it returns the words of sub29(zero, b, B); on a normalised value, the value.
+template <class Q>
+KZ_DEV F29<Q> norm29(const F29<Q>& a) {
+  F29<Q> r;
+  uint32_t c = 0;
+  _Pragma("unroll") for (int i = 0; i < Q::N; ++i) {
+    const uint32_t x = a.v[i] + c;
+    if (i < Q::N - 1) {
+      r.v[i] = x & M29;
+      c = x >> 29;
+    } else {
+      r.v[i] = x;
+    }
+  }
   return r;
 }
 
@@ -384,6 +404,20 @@ KZ_DEV F29<Q> canon29(const F29<Q>& a) {
   F29<Q> r;
   _Pragma("unroll") for (int i = 0; i < Q::N; ++i) r.v[i] = neg ? a.v[i] : d.v[i];
   return r;
+}
+
+// v is its own Montgomery product by ONE, mont29(v, ONE) = v word for word (v normalised): its two
+// top limbs t = v >> 29 (N - 2) lie in [PEEL_LO, p >> 29 (N - 2)), so PEEL_LO 2^(29 (N - 2)) <= v <
+// p -- the product is congruent to v and below v ONE / R29 + p, which leaves only v once v is at
+// least the threshold (tools/gen_params29.py peel_threshold; curves with a PEEL_LO).  A value that
+// a subtraction wrapped below zero has a top limb near 2^32 and fails the upper test.
+template <class Q>
+KZ_DEV bool peel_ok29(const F29<Q>& v) {
+  constexpr int N = Q::N;
+  const uint32_t t1 = v.v[N - 1], t0 = v.v[N - 2];
+  const bool lo = (t1 != 0) | (t0 >= Q::PEEL_LO);
+  const bool hi = (t1 < Q::MOD[N - 1]) | ((t1 == Q::MOD[N - 1]) & (t0 < Q::MOD[N - 2]));
+  return lo & hi;
 }
 
 // 32-bit words (value < 2^(32 NW)) <-> 29-bit limbs of the same integer

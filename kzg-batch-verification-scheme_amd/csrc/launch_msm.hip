@@ -87,7 +87,6 @@ void Launch<Cv>::row_items(hipStream_t st, const uint32_t* off, const uint32_t* 
   (void)hipMemsetAsync(rowq, 0, (size_t)RQ_WORDS * 4, st);
   const unsigned blocks = grid_for(nb, ITEMS_BLOCK);
   k_items_hist<<<blocks, 256, 0, st>>>(cnt, nb, L, rowq);
-  k_items_scan<<<1, 256, 0, st>>>(L, rowq);
   k_items_scatter<<<blocks, 256, 0, st>>>(off, cnt, nb, L, rowq, items, cap, cuts, cut_cap);
 }
 

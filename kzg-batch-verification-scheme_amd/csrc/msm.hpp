@@ -833,6 +833,11 @@ KZ_DEV Xyzz<Cv> x29_to32(const X29<Q>& a) {
 // profiles/r07/ab_fused_sub_bn254.txt), and what does not separate from noise is not kept.
 template <class Cv>
 constexpr bool kFusedSub = Cv::ID == 0;
+// The row loop's peeled first addition (acc_row29), per curve as well: it needs R29 / p large --
+// on BLS12-381 (2^25) a value fails the peel's range test once in 2^22, on BN254 (~169) a few per
+// cent would, and nearly every wave would fall back.  tools/gen_params29.py PEEL_FIRST, PEEL_LO.
+template <class Cv>
+constexpr bool kPeelFirst = Cv::ID == 0;
 
 // 2a (dbl-2008-s-1, a = 0).  Inputs within the record bounds; outputs x < 5.1p, y, zz, zzz <
 // 1.01p on BLS12-381; on BN254 (R29 / p ~ 169) x < 5.2p, y < 1.5p, zz, zzz < 1.1p (the same steps
@@ -944,7 +949,13 @@ KZ_DEV F29<Q> one_literals(std::integer_sequence<int, K...>) {
 // addition body on another schedule -- a copy, so that this kernel's code generation is not
 // touched by it: a change to the addition is made at both sites (the stage test of the row path
 // compares the two kernels' records word for word).  Sharing the body is a follow-up that has to
-// clear an A/B of k_accumulate first.
+// clear an A/B of k_accumulate first.  Where the two differ: acc_row29's hot loop negates q.y
+// limb by limb without a carry pass (neg_lazy29), which this loop cannot -- `if (inf)` below
+// copies q.y into the running sum at every bucket start, and the running sum holds normalised
+// values -- and acc_row29 peels an item's first addition (ZZ = ZZZ = ONE: no products by ONE) in
+// front of its loop, where every lane of a row is at that addition at once; here a bucket's
+// first addition is some iteration of the loop, another one in every lane.  The integers, and so
+// the records, are the same.
 template <class Cv>
 KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t chunk, uint32_t cur,
                        const uint32_t* __restrict__ sorted_val, const uint32_t* __restrict__ sorted_key,
@@ -1274,7 +1285,7 @@ __global__ void __launch_bounds__(256) k_fixup_crowded(const uint32_t* __restric
 // An item is (record, first entry, length <= L): a bucket of cnt <= L entries is one item whose
 // record is the bucket's own, a larger bucket is cut into ceil(cnt / L) items whose records are
 // piece slots behind the nb bucket records, joined by k_join_rows.  The items are counting-sorted
-// by length, descending (k_items_hist -> k_items_scan -> k_items_scatter), and a wave walks a row
+// by length, descending (k_items_hist -> k_items_scatter), and a wave walks a row
 // of 64 consecutive items in lockstep (k_accumulate_rows): every lane's first entry is the same
 // iteration, so the copy of a bucket's first point is a wave-uniform step with no addition
 // beside it (in k_accumulate the lane sits out an addition the other 63 run), nothing is flushed
@@ -1284,7 +1295,8 @@ __global__ void __launch_bounds__(256) k_fixup_crowded(const uint32_t* __restric
 // an item is summed by one lane in entry order, so no record depends on it.
 constexpr uint32_t ROW_LEN_MAX = 256;  // largest item length L a plan may ask for (the LDS histograms)
 // words of the per-launch row queue `rowq`: the row counter, the item count, the cut buckets and
-// the piece slots handed out so far, then the length histogram and the scatter cursors
+// the piece slots handed out so far, then the length histogram and the scatter cursors (items of
+// each length placed so far)
 enum : uint32_t {
   RQ_NEXT = 0, RQ_NITEMS = 1, RQ_NCUT = 2, RQ_PIECES = 3, RQ_HIST = 4, RQ_CUR = RQ_HIST + ROW_LEN_MAX + 1,
   RQ_WORDS = RQ_CUR + ROW_LEN_MAX + 1
@@ -1324,30 +1336,30 @@ static __global__ void __launch_bounds__(256) k_items_hist(const uint32_t* __res
     if (h[t]) atomicAdd(&rowq[RQ_HIST + t], h[t]);
 }
 
-// one workgroup: where each length class starts in the descending list, and the item count
-static __global__ void __launch_bounds__(256) k_items_scan(uint32_t L, uint32_t* __restrict__ rowq) {
-  __shared__ uint32_t h[ROW_LEN_MAX + 1];
-  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) h[t] = t ? rowq[RQ_HIST + t] : 0u;
-  __syncthreads();
-  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) {
-    uint32_t before = 0;  // items longer than t
-    for (uint32_t l = t + 1; l <= L; ++l) before += h[l];
-    rowq[RQ_CUR + t] = before;
-    if (t == 0) rowq[RQ_NITEMS] = before;
-  }
-}
-
 // the item list, three arrays of `cap` words: record, first entry, length.  An uncut bucket ranks
 // inside its workgroup by the LDS atomic's return and the workgroup reserves its run of every
 // class with one global atomic; a cut bucket (rare) takes its piece slots, its line of the join
 // list `cuts` (key, first piece slot, pieces; cut_cap lines) and its items' ranks from global atomics.
+// Where a length class starts in the descending list -- the items longer than it -- every workgroup
+// works out for itself from the finished histogram (257 words: cheaper than a one-workgroup scan
+// kernel between the two passes, a dependent launch in every batch's front end); the RQ_CUR
+// cursors count from zero inside their class.  Workgroup 0 leaves the item count in RQ_NITEMS.
 static __global__ void __launch_bounds__(256) k_items_scatter(const uint32_t* __restrict__ off,
                                                               const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t L,
                                                               uint32_t* __restrict__ rowq, uint32_t* __restrict__ items,
                                                               uint32_t cap, uint32_t* __restrict__ cuts, uint32_t cut_cap) {
-  __shared__ uint32_t h[ROW_LEN_MAX + 1], base[ROW_LEN_MAX + 1];
-  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) h[t] = 0;
+  __shared__ uint32_t h[ROW_LEN_MAX + 1], base[ROW_LEN_MAX + 1], all[ROW_LEN_MAX + 1], before[ROW_LEN_MAX + 1];
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) {
+    h[t] = 0;
+    all[t] = t ? rowq[RQ_HIST + t] : 0u;
+  }
   __syncthreads();
+  for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x) {
+    uint32_t s = 0;  // items longer than t
+    for (uint32_t l = t + 1; l <= L; ++l) s += all[l];
+    before[t] = s;
+    if (t == 0 && blockIdx.x == 0) rowq[RQ_NITEMS] = s;
+  }
   uint32_t c[ITEMS_PER_THREAD], rank[ITEMS_PER_THREAD];
 #pragma unroll
   for (uint32_t k = 0; k < ITEMS_PER_THREAD; ++k) {
@@ -1357,7 +1369,7 @@ static __global__ void __launch_bounds__(256) k_items_scatter(const uint32_t* __
   }
   __syncthreads();
   for (uint32_t t = threadIdx.x; t <= L; t += blockDim.x)
-    if (h[t]) base[t] = atomicAdd(&rowq[RQ_CUR + t], h[t]);
+    if (h[t]) base[t] = before[t] + atomicAdd(&rowq[RQ_CUR + t], h[t]);
   __syncthreads();
   auto put = [&](uint32_t pos, uint32_t rec, uint32_t first, uint32_t len) {
     if (pos >= cap) return;  // never: cap bounds the items of any count array (msm_plan.hpp row_items)
@@ -1383,7 +1395,7 @@ static __global__ void __launch_bounds__(256) k_items_scatter(const uint32_t* __
     cuts[3 * (size_t)line + 2] = np;
     for (uint32_t j = 0; j < np; ++j) {
       const uint32_t len = min(L, c[k] - j * L);
-      put(atomicAdd(&rowq[RQ_CUR + len], 1u), nb + slot + j, o + j * L, len);
+      put(before[len] + atomicAdd(&rowq[RQ_CUR + len], 1u), nb + slot + j, o + j * L, len);
     }
   }
 }
@@ -1396,7 +1408,17 @@ static __global__ void __launch_bounds__(256) k_items_scatter(const uint32_t* __
 // item starts on any 4-B boundary; the lanes of a row then fetch their next group in different
 // iterations of four, a masked issue of one load each).
 // The lambdas, the value streaming and the addition body are copied from acc_loop29, not shared with
-// it (see the note there): keep the two in step.
+// it (see the note there): keep the two in step.  Two differences, which leave every record word
+// for word what it was.  An item's first addition is peeled in front of the loop without its four
+// products by ONE (kPeelFirst, at its place below).  And the hot loop negates q.y lazily
+// (neg_lazy29: ACC_NEG - q.y limb by limb, 1
+// VALU per limb instead of sub29's carry pass).  There q.y is only an operand of R = q.y ZZZ - y,
+// and a product returns the words of the integer however its limbs carry it (column bound and top
+// limb: tools/gen_params29.py check_bounds, both curves).  Here a lane's y is never a copy of the
+// loop's q.y unnormalised: the first entry is loaded in front of the loop and the doubling's
+// entry behind it, both with sub29, and the restart after P + (-P) -- rare, per lane -- runs the
+// carry pass on the lazy form (norm29: the words of sub29).  acc_loop29 copies q.y into the
+// running sum at every bucket start of every lane, inside the loop, so it keeps sub29.
 template <class Cv>
 KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t* __restrict__ sorted_val,
                       const uint32_t* __restrict__ pts29, uint32_t* __restrict__ acc29) {
@@ -1423,10 +1445,16 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
       _Pragma("unroll") for (int k = 0; k < N; ++k) d[k] = a.v[k];
     }
   };
-  auto load_q = [&](uint32_t v, G& qx, G& qy) {
+  // lazy (compile-time at each call site): -y as ACC_NEG - y limb by limb, for the hot loop only
+  auto load_q = [&](uint32_t v, G& qx, G& qy, auto lazy) {
     load_pt29<Cv>(reinterpret_cast<const Affine<Cv>*>(pts29) + sv_point(v), qx, qy);
-    if (v & 1) qy = sub29(G::zero(), qy, Q::ACC_NEG);
+    if (v & 1) {
+      if constexpr (decltype(lazy)::value) qy = neg_lazy29(qy, Q::ACC_NEG);
+      else qy = sub29(G::zero(), qy, Q::ACC_NEG);
+    }
   };
+  constexpr std::false_type normalised{};
+  constexpr std::true_type lazy_neg{};
   auto set_one = [&]() {  // ONE from literal moves (acc_loop29)
     const G one = one_literals<Q>(std::make_integer_sequence<int, N / 2>{});
     st(s_zz, one);
@@ -1438,9 +1466,50 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
   G x, y;
   bool inf = false;
   // the item's first entry: running sum := its point
-  load_q(sorted_val[e], x, y);
-  set_one();
+  load_q(sorted_val[e], x, y, normalised);
   ++e;
+  // The item's first addition, peeled: ZZ = ZZZ = ONE here, and four of the body's ten products
+  // multiply by ONE.  A value v with PEEL_LO 2^(29 (N - 2)) <= v < p is its own product by ONE, word
+  // for word (field29.hpp peel_ok29), so with U2 = q.x, S2 = q.y or p - q.y, ZZ3 = canon29(PP) and
+  // ZZZ3 = canon29(PPP) the addition computes the integers of the generic body without them.  The
+  // four values miss the range about once in 2^22 each; P = 0 (the doubling, or P + (-P)) is as rare.
+  // If any lane of the wave that has a second entry meets one of these, the whole wave stores ONE
+  // and lets the loop below add the entry: one ballot, a wave-uniform branch, no per-lane path.  (Up
+  // to the ballot only LDS columns are written, which that ONE then overwrites.)
+  bool one = true;
+  if constexpr (kPeelFirst<Cv>) {
+    const bool two = e < end;
+    bool ok = true;
+    G R, PP, PPP;
+    if (two) {
+      const uint32_t v = sorted_val[e];
+      G qx, S2;
+      load_pt29<Cv>(reinterpret_cast<const Affine<Cv>*>(pts29) + sv_point(v), qx, S2);
+      if (v & 1) S2 = sub29(G::zero(), S2, Q::B1);  // p - q.y (q.y >= p wraps, and fails peel_ok29)
+      ok = peel_ok29(qx) & peel_ok29(S2);
+      const G P = sub29(qx, x, Q::ACC_P);
+      R = sub29(S2, y, Q::ACC_R);
+      ok &= !is_zero29_mf(P);
+      PP = sqr29(P);
+      const G zz = canon29(PP);
+      st(s_zz, zz);
+      PPP = mul29(P, PP);
+      const G zzz = canon29(PPP);
+      st(s_zzz, zzz);
+      ok &= peel_ok29(zz) & peel_ok29(zzz);
+    }
+    if (__ballot(two && !ok) == 0) {
+      if (two) {
+        const G Q2 = mul29(x, PP);
+        const G X3 = kFusedSub<Cv> ? sqrsub3_29(R, PPP, Q2, Q::ACC_X3) : sub3_29(sqr29(R), PPP, Q2, Q::ACC_X3);
+        y = mul2_29(R, sub29(Q2, X3, Q::ACC_QX), y, neg_lazy29(PPP, Q::ACC_PPP));
+        x = X3;
+        ++e;
+        one = false;
+      }
+    }
+  }
+  if (one) set_one();
   for (;;) {
     bool dbl = false;
     __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + (e & ~3u)), vq_wave, 16, 0, 0);
@@ -1454,10 +1523,10 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
         __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + e + 1), vq_wave, 16, 0, 0);
       }
       G qx, qy;
-      load_q(v, qx, qy);
+      load_q(v, qx, qy, lazy_neg);  // q.y: an operand of R's product only
       if (inf) {  // after P + (-P): this entry starts the sum again (rare, per lane)
         x = qx;
-        y = qy;
+        y = norm29(qy);  // the running sum holds normalised values
         set_one();
         inf = false;
         continue;
@@ -1483,7 +1552,7 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
     }
     if (!dbl) break;
     G qx, qy;  // entry e: running sum := 2 q (out of the hot loop, as in acc_loop29)
-    load_q(sorted_val[e], qx, qy);
+    load_q(sorted_val[e], qx, qy, normalised);
     asm volatile("" ::: "memory");
     const Xy29<Q> d = dbl_affine29<Q>(qx, qy, &s_zz[0][tx], &s_zzz[0][tx]);
     asm volatile("" ::: "memory");

@@ -68,9 +68,13 @@ def biased3(k, p, n):
     return b
 
 
-def check_bounds(p, n, nkp, roles):
-    """Value bounds (units of p) of the accumulation loop (msm.hpp acc_loop29), its doubling
-    (dbl_affine29), the record addition/doubling (x29_add, x29_dbl) and the on-curve test."""
+PEEL_FIRST = {"Bls12_381Fp29"}  # curves whose row loop peels an item's first addition (msm.hpp kPeelFirst)
+
+
+def check_bounds(p, n, nkp, roles, peel=False):
+    """Value bounds (units of p) of the accumulation loop (msm.hpp acc_loop29, acc_row29), its doubling
+    (dbl_affine29), the record addition/doubling (x29_add, x29_dbl) and the on-curve test; with
+    `peel` also the guard threshold of acc_row29's peeled first addition (peel_threshold)."""
     R = 1 << (W * n)
     lim = Fraction(R, p)  # values must stay representable: < 2^(29 n)
     def mont(a, b):       # (a p)(b p)/R + p, in units of p
@@ -91,6 +95,18 @@ def check_bounds(p, n, nkp, roles):
         addend = max(bias[:n - 1])
         assert addend < 1 << 31
         assert 2 * n * MASK * MASK + (1 << 35) + addend < 1 << 64, "fused column overflows"
+    def lazy_operand(bias, k, sub, addend):
+        # A product operand negated limb by limb, bias - b with no carry pass (field29.hpp
+        # neg_lazy29): b normalised and below sub p <= k p.  Limbs 0..n-2 land in (0, 2^30) because
+        # the bias limbs lie in [2^29, 2^30); the top limb must not go negative (unsigned limbs:
+        # only the top limb of a biased multiple can be smaller than the subtrahend's).  The column
+        # -- n limb products of a lazy limb (at most the largest bias limb) and a normalised one,
+        # n of m_i p_j, the carry (< 2^35) and the addend of a fused subtraction -- stays below 2^64.
+        assert k >= sub
+        assert bias[n - 1] >= (int(sub * p) >> (W * (n - 1))) + 1, "lazy top limb goes negative"
+        lazy = max(bias)
+        assert lazy < 1 << 30
+        assert n * lazy * MASK + n * MASK * MASK + (1 << 35) + addend < 1 << 64, "lazy column overflows"
     ro = {k: Fraction(v) for k, v in roles.items()}
     # points come out of a Montgomery product with canonical inputs (fp_to29, k_convert_points
     # <To29>): below (p / R29 + 1) p, NOT below p -- on BN254 that is 1.006 p, so negating q.y
@@ -114,6 +130,11 @@ def check_bounds(p, n, nkp, roles):
         assert ro["ACC_P"] >= X and ro["ACC_R"] >= Y
         fused(biased(roles["ACC_P"], p, n), ro["ACC_P"], X)   # P = mulsub29(q.x, zz, x)
         fused(biased(roles["ACC_R"], p, n), ro["ACC_R"], Y)   # R = mulsub29(q.y, zzz, y)
+        # acc_row29's hot loop: a negated q.y enters that product as ACC_NEG - q.y limb by limb (the
+        # point's y < qin p), beside ZZZ < Z p normalised and, where the subtraction is fused, its
+        # ACC_R limb; the same integer as sub29's form, so the bounds of R above hold as they are
+        assert Z < lim
+        lazy_operand(biased(roles["ACC_NEG"], p, n), ro["ACC_NEG"], qin, max(biased(roles["ACC_R"], p, n)[:n - 1]))
         P, Rr = U2 + ro["ACC_P"], S2 + ro["ACC_R"]
         assert P < nkp and Rr < nkp, "zero test range"
         PP = mont(P, P); PPP = mont(P, PP); Q2 = mont(X, PP)
@@ -158,7 +179,39 @@ def check_bounds(p, n, nkp, roles):
     # k_convert_points<To29>: y^2 - (x^3 + b) with B4, zero-tested
     rhs = mont(mont(1, 1), 1) + 1
     assert 4 >= rhs and mont(1, 1) + 4 < nkp
-    return dict(X=float(X), Y=float(Y), Z=float(Z))
+    out = dict(X=float(X), Y=float(Y), Z=float(Z))
+    if peel:
+        out["PEEL_LO"] = peel_threshold(p, n, roles, qin, mont)
+    return out
+
+
+def peel_threshold(p, n, roles, qin, mont):
+    """acc_row29's peeled first addition (ZZ = ZZZ = ONE): the four products by ONE = R29 mod p are
+    replaced by the value itself.  For a < k p, mont(a, ONE) = (a ONE + m p) / R29 with m < R29 is
+    congruent to a and below a ONE / R29 + p, so it is a's canonical residue c unless c < a ONE /
+    R29: c >= T = ceil(k p ONE / R29) is enough.  The four values: q.x (< qin p; U2 = q.x needs q.x
+    < p too), q.y or its negation (< ACC_NEG p; S2 = q.y or p - q.y needs q.y < p), PP and PPP (<
+    2 p, canon29's range) -- k = ACC_NEG covers all four.  The kernel tests the two top limbs t =
+    v >> 29 (n - 2): t >= PEEL_LO makes v >= T, t < p >> 29 (n - 2) makes v < p (a q.y >= p under
+    a negation wraps p - q.y to a top limb of 2^32 - 1, which fails it).  -> PEEL_LO."""
+    R = 1 << (W * n)
+    ro = {k: Fraction(v) for k, v in roles.items()}
+    x, y = qin, ro["ACC_NEG"]                    # the prologue's copy: the first point, y negated or not
+    assert ro["ACC_P"] >= x and ro["ACC_R"] >= y  # P = sub29(q.x, x, ACC_P), R = sub29(S2, y, ACC_R)
+    # (S2 = sub29(0, q.y, B1) needs q.y <= p: the guard's own condition, tested on the result)
+    P = qin + ro["ACC_P"]
+    PP = mont(P, P); PPP = mont(P, PP)
+    assert PP < 2 and PPP < 2, "canon29's range"
+    k = ro["ACC_NEG"]
+    assert k >= max(qin, PP, PPP)
+    T = -(-int(k) * p * (R % p) // R)
+    shift = W * (n - 2)
+    lo = -(-T // (1 << shift))
+    assert lo << shift >= T and lo < 1 << W, "the threshold has to sit in limb n - 2"
+    # a wave of 64 lanes x 4 values falls back when one of them lies below the threshold or shares
+    # p's two top limbs: rarer than once in 2^10 waves
+    assert 256 * ((lo + 1) << shift) * (1 << 10) < p
+    return lo
 
 
 def arr(v):
@@ -168,7 +221,7 @@ def arr(v):
 def emit(name, p, n, r32, b, nkp, roles):
     R29 = 1 << (W * n)
     assert p < R29 and (n - 1) * W < p.bit_length()
-    bounds = check_bounds(p, n, nkp, roles)
+    bounds = check_bounds(p, n, nkp, roles, peel=name in PEEL_FIRST)
     inv = (-pow(p, -1, 1 << 32)) % (1 << 32)
     print("struct %s {  // R29 = 2^%d; loop bounds x < %.2fp, y < %.2fp, zz, zzz < %.2fp"
           % (name, W * n, bounds["X"], bounds["Y"], bounds["Z"]))
@@ -194,6 +247,11 @@ def emit(name, p, n, r32, b, nkp, roles):
         print("  static constexpr const uint32_t (&%s)[N] = %s%d;" % (role, kind, k))
     print("  static constexpr const uint32_t (&ACC_X3_B)[N] = B%d;  // ACC_X3 for two carry passes (A/B build)"
           % roles["ACC_X3"])
+    if "PEEL_LO" in bounds:
+        print("  static constexpr uint32_t PEEL_LO = %d;  // acc_row29's peeled first addition: a value whose top two"
+              % bounds["PEEL_LO"])
+        print("  // limbs v >> %d lie in [PEEL_LO, p >> %d) is its own product by ONE (check_bounds peel_threshold)"
+              % (W * (n - 2), W * (n - 2)))
     print("  static constexpr int NKP = %d;" % nkp)
     print("  static constexpr uint32_t KP_LO[NKP] = %s;  // low limb of k p" % arr([(k * p) & MASK for k in range(nkp)]))
     print("  static constexpr uint32_t KP[NKP][N] = {%s};  // k p" % ", ".join(arr(limbs(k * p, n)) for k in range(nkp)))

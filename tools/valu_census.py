@@ -72,7 +72,16 @@ def main():
     n_limbs = 14 if curve == "bls12_381" else 9
     bl = blocks(path, sym)
     # the first copy of the loop: the blocks with >= 300 mads, and the negation block before them
-    hot = [i for i, (_, ops) in enumerate(bl) if sum(o == "v_mad_u64_u32" for o in ops) >= 300][:2]
+    # (the row kernel has one copy of the loop, behind the blocks of an item's peeled first addition,
+    # which hold >= 300 mads each as well: its loop is the last two such blocks)
+    heavy = [i for i, (_, ops) in enumerate(bl) if sum(o == "v_mad_u64_u32" for o in ops) >= 300]
+    hot = heavy[-2:] if rows else heavy[:2]
+    if rows and len(heavy) > 2:
+        peel = Counter(o for i in heavy[:-2] for o in bl[i][1])
+        print("k_accumulate_rows<%s> peeled first addition, blocks %s: %d instructions, %d VALU, %d v_mad_u64_u32, %d scratch"
+              % (curve, ", ".join(bl[i][0] for i in heavy[:-2]), sum(peel.values()),
+                 sum(k for op, k in peel.items() if op.startswith("v_")), peel["v_mad_u64_u32"],
+                 sum(k for op, k in peel.items() if op.startswith("scratch"))))
     neg = hot[0] - 1
     while sum(o.startswith("global_load") for o in bl[neg][1]) == 0:
         neg -= 1
