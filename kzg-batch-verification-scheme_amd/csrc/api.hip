@@ -8,12 +8,11 @@
 // (no CPU fallback).
 // Reference: none (LICENSE only); boundary contract = SURVEY.md 8b, BASELINE.json:5.
 #include "host.hpp"
+#include "copy_pool.hpp"
 
 #include <sys/random.h>
-#include <condition_variable>
 #include <map>
 #include <mutex>
-#include <thread>
 #define KZ_STR2(x) #x
 #define KZ_STR(x) KZ_STR2(x)
 
@@ -140,76 +139,13 @@ bool host_pinned(const void* p, size_t bytes) {
   return a >= it->first && a + bytes <= it->second.hi;
 }
 
-// Parallel memcpy for pageable -> pinned staging: one memcpy thread reaches ~10-20 GB/s, below
-// PCIe Gen5's ~50 GB/s, so the copy is split over KZGMI_COPY_THREADS workers (default 8) plus
-// the caller.  One job at a time (contexts on several host threads take turns).
-class CopyPool {
- public:
-  CopyPool() {
+// The staging copy's pool (copy_pool.hpp): KZGMI_COPY_THREADS threads, the caller included
+// (default 8), fixed at the first staged copy of the process.
+kzgmi::CopyPool* copy_pool() {
+  static kzgmi::CopyPool* p = [] {  // never destroyed: its workers are detached
     const char* e = getenv("KZGMI_COPY_THREADS");
-    nthreads_ = e ? std::max(1, atoi(e)) : 8;
-  }
-  void copy(void* dst, const void* src, size_t len) {
-    if (len < (size_t(2) << 20) || nthreads_ <= 1) {
-      memcpy(dst, src, len);
-      return;
-    }
-    std::lock_guard<std::mutex> job(job_mu_);
-    start();
-    const int parts = (int)workers_.size() + 1;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      dst_ = (uint8_t*)dst;
-      src_ = (const uint8_t*)src;
-      len_ = len;
-      parts_ = parts;
-      left_ = parts - 1;
-      ++gen_;
-    }
-    cv_.notify_all();
-    part(0);
-    std::unique_lock<std::mutex> lk(mu_);
-    done_.wait(lk, [&] { return left_ == 0; });
-  }
-
- private:
-  void start() {
-    if (!workers_.empty()) return;
-    for (int i = 1; i < nthreads_; ++i) {
-      workers_.emplace_back([this, i] { loop(i); });
-      workers_.back().detach();  // the pool lives as long as the process (never destroyed)
-    }
-  }
-  void part(int i) {
-    const size_t per = (len_ / parts_ + 63) & ~size_t(63);
-    const size_t lo = std::min(len_, per * i), hi = std::min(len_, per * (i + 1));
-    if (hi > lo) memcpy(dst_ + lo, src_ + lo, hi - lo);
-  }
-  void loop(int i) {
-    uint64_t seen = 0;
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return gen_ != seen; });
-        seen = gen_;
-      }
-      part(i);
-      std::lock_guard<std::mutex> lk(mu_);
-      if (--left_ == 0) done_.notify_one();
-    }
-  }
-  int nthreads_ = 8;  // fixed by the constructor (the pool is a function-local static: thread-safe)
-  std::mutex job_mu_, mu_;
-  std::condition_variable cv_, done_;
-  std::vector<std::thread> workers_;
-  uint8_t* dst_ = nullptr;
-  const uint8_t* src_ = nullptr;
-  size_t len_ = 0;
-  int parts_ = 1, left_ = 0;
-  uint64_t gen_ = 0;
-};
-CopyPool* copy_pool() {
-  static CopyPool* p = new CopyPool();  // never destroyed: its workers are detached
+    return new kzgmi::CopyPool(e ? std::max(1, atoi(e)) : 8);
+  }();
   return p;
 }
 }  // namespace

@@ -42,3 +42,56 @@ def test_no_stale_ab_knobs():
             with open(os.path.join(csrc, f)) as fh:
                 found |= set(re.findall(r"\bKZ_[A-Z0-9_]+", fh.read()))
     assert found <= allowed, sorted(found - allowed)
+
+
+def _env_knobs():
+    """Every KZGMI_* environment variable the library reads: the getenv("KZGMI_...") names in csrc/."""
+    import re
+    names = set()
+    csrc = os.path.join(PKG, "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hpp", ".hip")):
+            with open(os.path.join(csrc, f)) as fh:
+                names |= set(re.findall(r'getenv\(\s*"(KZGMI_[A-Z0-9_]+)"\s*\)', fh.read()))
+    return names
+
+
+def _env_names_set_by(path):
+    """The KZGMI_* names a Python file sets: keyword arguments of calls (a context-creation helper,
+    os.environ.update, dict), keys of dict displays, and subscripts that are assigned to.  Prose in
+    docstrings and comments does not count."""
+    import ast
+    with open(path) as fh:
+        tree = ast.parse(fh.read(), path)
+    names = set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Call):
+            names |= {k.arg for k in node.keywords if k.arg}
+        elif isinstance(node, ast.Dict):
+            names |= {k.value for k in node.keys if isinstance(k, ast.Constant) and isinstance(k.value, str)}
+        elif isinstance(node, (ast.Assign, ast.AugAssign)):
+            for t in (node.targets if isinstance(node, ast.Assign) else [node.target]):
+                key = t.slice if isinstance(t, ast.Subscript) else None
+                if isinstance(key, ast.Constant) and isinstance(key.value, str):
+                    names.add(key.value)
+    return {n for n in names if n.startswith("KZGMI_")}
+
+
+def test_every_env_knob_has_a_test_and_a_documentation_line():
+    """A form that only an environment variable selects is run by some test and told to the user:
+    every getenv("KZGMI_...") name of csrc/ is set by at least one file under tests/ and is named
+    in include/kzgmi.h or INTEGRATION.md."""
+    import re
+    knobs = _env_knobs()
+    assert len(knobs) >= 23, sorted(knobs)  # the scan itself still finds them
+    set_in_tests = set()
+    tests = os.path.join(ROOT, "tests")
+    for f in sorted(os.listdir(tests)):
+        if f.endswith(".py"):
+            set_in_tests |= _env_names_set_by(os.path.join(tests, f))
+    documented = set()
+    for path in (os.path.join(ROOT, "include", "kzgmi.h"), os.path.join(ROOT, "INTEGRATION.md")):
+        with open(path) as fh:
+            documented |= set(re.findall(r"\bKZGMI_[A-Z0-9_]+", fh.read()))
+    assert not knobs - set_in_tests, "no test sets: %s" % sorted(knobs - set_in_tests)
+    assert not knobs - documented, "neither kzgmi.h nor INTEGRATION.md names: %s" % sorted(knobs - documented)
