@@ -70,7 +70,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * and the EIP-4844 producer entry points kzgmi_blob_pk_*, kzgmi_blob_commit*, kzgmi_compute_kzg_proofs*,
  * kzgmi_compute_blob_proofs*, kzgmi_blob_quotient_device, and the search entry points
  * kzgmi_batch_check_partials_device, kzgmi_batch_range_partials_device, kzgmi_batch_find_invalid*,
- * kzgmi_verify_blob_batch_find_invalid*, kzgmi_find_invalid_stats.
+ * kzgmi_verify_blob_batch_find_invalid*, kzgmi_find_invalid_stats, and the cell search entry points
+ * kzgmi_cell_coeffs_device, kzgmi_cell_range_partials_device, kzgmi_verify_cell_batch_find_invalid*.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -409,6 +410,48 @@ int kzgmi_verify_cell_batch_device_async(kzgmi_ctx* ctx, const kzgmi_cell_srs* s
                                          const void* d_commitments48, size_t m, const void* d_commitment_indices,
                                          const void* d_cell_indices, const void* d_cells, const void* d_proofs48,
                                          size_t n, const uint8_t* r32);
+/* Locating the invalid cells of a rejected cell batch (the search of "locating the invalid tuples"
+ * below, with its conventions: synchronous, slot 0 idle, the context's primary device, an input
+ * error -- encoding, curve, subgroup, a cell element >= r, a cell index >= 128, a commitment index
+ * >= m -- is the return code with the outputs untouched).  Cell k is invalid iff
+ *   e(pi_k, [tau^64]_2) != e(C_{commitment_indices[k]} + z_k pi_k - [I_k(tau)]_1, [1]_2),  z_k = h_{cell_indices[k]}^64;
+ * duplicate (commitment, cell) pairs are legal and every index is judged on its own.  A range g of
+ * indices passes iff e(A_g, [tau^64]_2) e(-B_g, [1]_2) = 1 for
+ *   A_g = sum_{k in g} r_k pi_k,
+ *   B_g = sum_{k in g} r_k C_{cidx[k]} + sum_{k in g} (r_k z_k) pi_k - sum_{m < 64} c_m(g) [tau^m]_1,
+ *   c_m(g) = sum_{k in g} r_k coef_k[m]   (coef_k: the 64 coefficients of I_k),
+ * r_k the 127-bit counter-mode randomiser of the global index k:
+ *   r_k = int_be(SHA256(seed32 || le64(k))[0:16]) >> 1, 1 if that is 0
+ * (seed32 == NULL: drawn from the OS CSPRNG).  Every level of the search runs in the grouped
+ * one-wave-per-term kernel (3 len + 64 terms per range), so a call takes n <= 65536 cells (and
+ * m <= 65536 commitments): more is KZGMI_ERR_ARG.  bad_out, max_bad (1 .. 4096), n_bad_out, more_out
+ * and n == 0 are as in kzgmi_batch_find_invalid; kzgmi_find_invalid_stats reports the search
+ * (bucket jobs: 0, wave-terms: the sum of 3 len + 64 over every tested range).  The host form stages
+ * like kzgmi_verify_cell_batch.
+ * kzgmi_cell_coeffs_device (diagnostic): c_m of I_k for every cell -> d_coeffs_out, n x 64 x 32 B
+ * big-endian, coefficient m of cell k at byte 32 (64 k + m); n <= 65536.
+ * kzgmi_cell_range_partials_device: (A_g, B_g) of n_ranges index ranges of one device-resident cell
+ * batch whose first cell has global index index_offset, 2 records per range -> d_partials_out;
+ * ranges, bounds and errors as kzgmi_batch_range_partials_device (the 256 MiB of trees hold about
+ * 160 000 cells over all ranges). */
+int kzgmi_cell_coeffs_device(kzgmi_ctx* ctx, const void* d_cell_indices, const void* d_cells, size_t n,
+                             void* d_coeffs_out);
+int kzgmi_cell_range_partials_device(kzgmi_ctx* ctx, const kzgmi_cell_srs* srs, const void* d_commitments48, size_t m,
+                                     const void* d_commitment_indices, const void* d_cell_indices,
+                                     const void* d_cells, const void* d_proofs48, size_t n, uint64_t index_offset,
+                                     const uint8_t* seed32, const uint64_t* ranges, size_t n_ranges,
+                                     void* d_partials_out);
+int kzgmi_verify_cell_batch_find_invalid(kzgmi_ctx* ctx, const kzgmi_cell_srs* srs, const uint8_t* commitments48,
+                                         size_t m, const uint64_t* commitment_indices, const uint64_t* cell_indices,
+                                         const uint8_t* cells, const uint8_t* proofs48, size_t n,
+                                         const uint8_t* seed32, uint64_t* bad_out, size_t max_bad, size_t* n_bad_out,
+                                         int* more_out);
+int kzgmi_verify_cell_batch_find_invalid_device(kzgmi_ctx* ctx, const kzgmi_cell_srs* srs,
+                                                const void* d_commitments48, size_t m,
+                                                const void* d_commitment_indices, const void* d_cell_indices,
+                                                const void* d_cells, const void* d_proofs48, size_t n,
+                                                const uint8_t* seed32, uint64_t* bad_out, size_t max_bad,
+                                                size_t* n_bad_out, int* more_out);
 
 /* ---- EIP-7594 cell extension and recovery (compute_cells, and the cells of
  * recover_cells_and_kzg_proofs; the proofs: the next section) -- BLS12-381 only, with the cell

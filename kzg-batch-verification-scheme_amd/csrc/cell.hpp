@@ -148,6 +148,65 @@ static __global__ void __launch_bounds__(64) k_cell_fold_intt(const uint64_t* __
   part[c * CELL_N + j] = fp_mul(s, x[j]);
 }
 
+// The 64 coefficients of every cell's own interpolation polynomial I_k, unfolded (the search for a
+// rejected batch's invalid cells weights them per index range: msm_group.hpp k_cell_range_fold):
+// one wave per cell, lane j element j, four cells per workgroup; the same six stages and scale as
+// k_cell_fold_intt.  coef_le[(64 k + m) 8 ..]: c_m as 8 LE words in standard form; coeffs_be (may
+// be null): c_m as 32 B big-endian at 32 (64 k + m).  Every element is range-checked here, once
+// (DERR_SCALAR, counts as 0); a cell index out of range reads coset 0 (k_cell_z raises it).
+constexpr uint32_t CELL_COEFF_PACK = 4;  // cells per workgroup
+static __global__ void __launch_bounds__(64 * CELL_COEFF_PACK) k_cell_coeffs(
+    const uint64_t* __restrict__ cell_indices, const uint8_t* __restrict__ cells, uint32_t n,
+    const BlobF* __restrict__ table, uint32_t* __restrict__ coef_le, uint8_t* __restrict__ coeffs_be,
+    uint32_t* __restrict__ err) {
+  __shared__ BlobF xs[CELL_COEFF_PACK][CELL_N];
+  const uint32_t wv = threadIdx.x >> 6, j = threadIdx.x & 63u;
+  const uint32_t k = blockIdx.x * CELL_COEFF_PACK + wv;
+  const bool live = k < n;  // wave-uniform; the waves past the last cell keep the barriers
+  BlobF* x = xs[wv];
+  BlobF e = BlobF::zero();
+  uint32_t c = 0;
+  if (live) {
+    const uint64_t ci = cell_indices[k];
+    c = ci < CELL_COSETS ? (uint32_t)ci : 0u;
+    uint32_t we[8];
+    load_words(cells + (size_t)k * CELL_BYTES + 32 * j, we);
+    e = fp_from_be_words<BlobR>(we, 0);
+    if (!fp_raw_lt_mod(e)) {
+      raise_err(err, DERR_SCALAR);
+      e = BlobF::zero();
+    }
+  }
+  x[j] = e;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t half = 1; half < CELL_N; half <<= 1) {
+    const BlobF w = table[CELL_T_TW + (j & (half - 1)) * (CELL_N / (2 * half))];
+    const bool up = (j & half) != 0;
+    const BlobF a = x[up ? j - half : j];
+    const BlobF b = fp_mul(w, x[up ? j : j + half]);
+    const BlobF y = up ? fp_sub(a, b) : fp_add(a, b);
+    __syncthreads();
+    x[j] = y;
+    __syncthreads();
+  }
+  if (!live) return;
+  // 64^-1 h_c^-m, m = j (6 bits)
+  BlobF hp = table[CELL_T_HINV + c], s = table[CELL_T_INV64];
+  for (int q = 0; q < 6; ++q) {
+    if ((j >> q) & 1) s = fp_mul(s, hp);
+    hp = fp_sqr(hp);
+  }
+  const BlobF cm = fp_mul(s, x[j]);  // the Montgomery scale times the standard-form sum: standard form
+  const size_t o = (size_t)k * CELL_N + j;
+  store_words(reinterpret_cast<uint8_t*>(coef_le + 8 * o), cm.v);
+  if (coeffs_be) {
+    uint32_t w[8];
+    fp_to_be_words(cm, w, 0);
+    store_words(coeffs_be + 32 * o, w);
+  }
+}
+
 // c_m = sum over the cosets of part[c][m].  neg_le: -c_m as 8 LE words in standard form (the
 // scalars of MSM#1's [tau^m]_1 class); coeffs_be (may be null): c_m as 32 B big-endian.
 static __global__ void __launch_bounds__(64) k_cell_sum(const BlobF* __restrict__ part, uint32_t* __restrict__ neg_le,

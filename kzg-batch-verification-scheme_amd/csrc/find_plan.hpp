@@ -82,8 +82,9 @@ inline FindLevel find_next_level(const FindRange* parts, const int32_t* ok, size
 }
 
 // One group of a grouped launch as the kernel reads it (device memory): tuples [lo, lo + len) of the
-// resident batch, its waves [wave_base, wave_base + 3 len + 1), and of its trees A (len leaves) and
-// B (2 len + 1 leaves) the first stored node and the first arrival counter
+// resident batch, its waves [wave_base, wave_base + 3 len + T), and of its trees A (len leaves) and
+// B (2 len + T leaves) the first stored node and the first arrival counter.  T is the tail: 1 for
+// opening tuples (-t_g G1), 64 for EIP-7594 cells (-c_m(g) [tau^m]_1, m < 64)
 struct FindGroup {
   uint32_t lo, len, wave_base;
   uint32_t node_base[2], flag_base[2];
@@ -99,10 +100,11 @@ inline void find_tree_size(uint64_t leaves, uint64_t& nodes, uint64_t& flags) {
     flags += (cnt + 1) >> 1;
   }
 }
-inline uint64_t find_wave_terms(uint64_t len) { return 3 * len + 1; }
+inline uint64_t find_wave_terms(uint64_t len, uint32_t tail = 1) { return 3 * len + tail; }
 
 // The launch of G groups: group g's waves in the order r_i pi_i (A's leaves 0 .. len - 1), r_i C_i
-// (B's leaves 0 .. len - 1), s_i pi_i (B's leaves len .. 2 len - 1), -t_g G1 (B's leaf 2 len).
+// (B's leaves 0 .. len - 1), s_i pi_i (B's leaves len .. 2 len - 1), then the `tail` terms of the
+// group's own scalars (B's leaves 2 len .. 2 len + tail - 1): -t_g G1, or the 64 of a cell range.
 // ranges are relative to the resident batch.  table (G entries, may be null: sizes only).
 // fits: every index stays below 2^31.
 struct FindGroupPlan {
@@ -111,17 +113,17 @@ struct FindGroupPlan {
   size_t bytes;  // the tree workspace FindTuning::group_bytes bounds: nodes + flags
   bool fits;
 };
-inline FindGroupPlan find_group_plan(const FindRange* ranges, size_t G, FindGroup* table) {
+inline FindGroupPlan find_group_plan(const FindRange* ranges, size_t G, FindGroup* table, uint32_t tail = 1) {
   FindGroupPlan p{};
   for (size_t g = 0; g < G; ++g) {
     const uint64_t len = ranges[g].hi - ranges[g].lo;
     uint64_t na, fa, nb, fb;
     find_tree_size(len, na, fa);
-    find_tree_size(2 * len + 1, nb, fb);
+    find_tree_size(2 * len + tail, nb, fb);
     if (table)  // (meaningless where the plan does not fit: the caller refuses it)
       table[g] ={(uint32_t)ranges[g].lo, (uint32_t)len, (uint32_t)p.waves,
                   {(uint32_t)p.nodes, (uint32_t)(p.nodes + na)}, {(uint32_t)p.flags, (uint32_t)(p.flags + fa)}, 0};
-    p.waves += find_wave_terms(len);
+    p.waves += find_wave_terms(len, tail);
     p.nodes += na + nb;
     p.flags += fa + fb;
   }
@@ -129,7 +131,7 @@ inline FindGroupPlan find_group_plan(const FindRange* ranges, size_t G, FindGrou
   p.bytes_nodes = (size_t)(p.nodes + 1) * SMALL_NODE_WORDS * 4;
   p.bytes_flags = (size_t)(p.flags + 1) * 4;
   p.bytes_table = (G + 1) * sizeof(FindGroup);
-  p.bytes_negt = (G + 1) * 32;
+  p.bytes_negt = ((size_t)tail * G + 1) * 32;
   p.bytes = p.bytes_nodes + p.bytes_flags;
   return p;
 }
@@ -157,17 +159,17 @@ inline uint32_t find_level_fanout(const FindRange* suspects, size_t ns, const Fi
 }
 
 // How many of ranges[0, G) one grouped launch takes within the workspace bound: at least one
-inline size_t find_group_chunk(const FindRange* ranges, size_t G, const FindTuning& t) {
+inline size_t find_group_chunk(const FindRange* ranges, size_t G, const FindTuning& t, uint32_t tail = 1) {
   uint64_t nodes = 0, flags = 0, waves = 0;
   size_t g = 0;
   for (; g < G; ++g) {
     const uint64_t len = ranges[g].hi - ranges[g].lo;
     uint64_t na, fa, nb, fb;
     find_tree_size(len, na, fa);
-    find_tree_size(2 * len + 1, nb, fb);
+    find_tree_size(2 * len + tail, nb, fb);
     nodes += na + nb;
     flags += fa + fb;
-    waves += find_wave_terms(len);
+    waves += find_wave_terms(len, tail);
     if (g > 0 && ((nodes + 1) * SMALL_NODE_WORDS * 4 + (flags + 1) * 4 > t.group_bytes || waves >= (1ull << 31))) break;
   }
   return g;

@@ -102,6 +102,7 @@ struct Slot {
   DevBuf blob_z, blob_y;                         // blob batches: the derived z_i, y_i (n x 32 B each);
                                                  // cell batches: z_k = h_k^64 and y_k = 0
   DevBuf cell_part, cell_coef;                   // cell batches: per-coset coefficients; -c_m (64 x 8 LE words)
+  DevBuf cell_tab;                               // the search for invalid cells: c_m of every I_k (n x 64 x 8 LE words)
   DevBuf rec_z;                                  // recover_cells: the call's vanishing-polynomial table (recover.hpp)
   DevBuf fk_coef, fk_scal, fk_a, fk_b, fk_enc;   // cell proofs (fk20.hpp): coefficients, ahat, two point vectors, encodings
   DevBuf bp_q, bp_part, bp_enc;                  // blob proofs (blobproof.hpp): quotients, partial sums and results, encodings
@@ -116,7 +117,7 @@ struct Slot {
   // MsmTuning::split_rev) reduces and combines on the context's one side stream beside the second
   // launch; side_ev[0] = the first launch's sets accumulated, [1] = its MSM combined
   hipEvent_t side_ev[2] = {};
-  int* host_flags = nullptr;  // pinned: [ok, err]
+  int* host_flags = nullptr;  // pinned, 4 words: [ok, err, the cell search's front-end error (host_find.hip)]
   uint8_t* host_out = nullptr;  // pinned: encoded MSM result of an async MSM job
   uint8_t* ring[2] = {};        // pinned staging of pageable host inputs (kRingBytes each, lazily)
   hipEvent_t ring_ev[2] = {};   // the DMA that last read ring[b]
@@ -134,7 +135,7 @@ struct Slot {
     DevBuf* bufs[] = {&pts, &inf, &scal_r, &scal_s, &scal_t, &tpart, &cnt, &off, &coarse, &ent, &total, &sval, &skey,
                       &R, &U, &scratch, &winsum, &res, &flags, &stage, &outb, &acc29, &accq, &crowd, &rowq, &items, &cuts, &fs_leaves,
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
-                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &rec_z,
+                      &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &cell_tab, &rec_z,
                       &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc,
                       &find_tab, &find_negt, &find_nodes, &find_flags, &find_rec, &find_ok};
     for (DevBuf* b : bufs) f(*b);
@@ -410,6 +411,16 @@ int ensure_once(bool& ready, DevBuf& buf, size_t bytes, hipStream_t st, F&& laun
   HIPCHK(hipStreamSynchronize(st));
   ready = true;
   return 0;
+}
+
+// the cell coset table of this context's device (cell.hpp), built at the first call that reads it
+inline int ensure_cell_table(kzgmi_ctx* c, hipStream_t st) {
+  return ensure_once(c->cell_table_ready, c->cell_table, CellLaunch::table_bytes(), st,
+                     [&] { CellLaunch::table(st, c->cell_table.p); });
+}
+// a live cell SRS of this context (an SRS of another kind, or of another context, is not in the list)
+inline bool is_cell_srs(const kzgmi_ctx* c, const kzgmi_cell_srs* cs) {
+  return cs && std::find(c->cell_srs_list.begin(), c->cell_srs_list.end(), cs) != c->cell_srs_list.end();
 }
 
 // A synchronous utility job on slot s whose kernels report through the slot's error word:

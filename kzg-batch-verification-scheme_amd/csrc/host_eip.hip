@@ -8,14 +8,11 @@ constexpr size_t kBlobMax = size_t(1) << 20;  // blobs per call
 constexpr uint32_t kBlobFlags = KZGMI_FLAG_POWERS | KZGMI_FLAG_COMPRESSED | KZGMI_FLAG_SUBGROUP_CHECK;
 
 // the tables of this context's device, built at the first call that reads them (on st, waited
-// for): the blob evaluation domain, the cell coset table, the transforms' twiddles and scale factors
+// for): the blob evaluation domain, the cell coset table (host.hpp ensure_cell_table), the transforms'
+// twiddles and scale factors
 int ensure_blob_table(kzgmi_ctx* c, hipStream_t st) {
   return ensure_once(c->blob_table_ready, c->blob_table, BlobLaunch::table_bytes(), st,
                      [&] { BlobLaunch::domain(st, c->blob_table.p); });
-}
-int ensure_cell_table(kzgmi_ctx* c, hipStream_t st) {
-  return ensure_once(c->cell_table_ready, c->cell_table, CellLaunch::table_bytes(), st,
-                     [&] { CellLaunch::table(st, c->cell_table.p); });
 }
 int ensure_ntt_table(kzgmi_ctx* c, hipStream_t st) {
   return ensure_once(c->ntt_table_ready, c->ntt_table, RecoverLaunch::table_bytes(), st,
@@ -120,11 +117,6 @@ int kzgmi_verify_blob_batch(kzgmi_ctx* c, const kzgmi_srs* srs, const uint8_t* b
 }  // extern "C"
 namespace {
 constexpr size_t kCellMax = size_t(1) << 20;  // cells (and unique commitments) per call
-
-// a live cell SRS of this context (an SRS of another kind, or of another context, is not in the list)
-bool is_cell_srs(const kzgmi_ctx* c, const kzgmi_cell_srs* cs) {
-  return cs && std::find(c->cell_srs_list.begin(), c->cell_srs_list.end(), cs) != c->cell_srs_list.end();
-}
 
 Seed seed_of(const uint8_t* r32) {
   uint8_t sb[32];

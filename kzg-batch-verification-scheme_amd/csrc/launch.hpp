@@ -123,6 +123,12 @@ struct Launch {
                         const Seed& seed, uint64_t index_offset, const uint8_t* ys, const uint32_t* scal_r,
                         const uint32_t* scal_s, uint32_t* negt, const AF* pts, const uint8_t* inf, uint32_t* nodes,
                         uint32_t* flags, size_t flag_words, XY* res);
+  // ... of G index ranges of a resident batch of n EIP-7594 cells (BLS12-381 only): points
+  // [pi | C | tau^m (64)], coef: CellLaunch::coeffs' table; negt: G x 64 x 8 words of scratch, filled here
+  static void group_msm_cells(hipStream_t st, const FindGroup* table, uint32_t G, uint32_t waves, uint32_t n,
+                              const Seed& seed, uint64_t index_offset, const uint32_t* coef, const uint32_t* scal_r,
+                              const uint32_t* scal_s, uint32_t* negt, const AF* pts, const uint8_t* inf,
+                              uint32_t* nodes, uint32_t* flags, size_t flag_words, XY* res);
   // count records become marked when *err != 0; a marked record among them raises its code into *err
   static void mark_records(hipStream_t st, XY* recs, uint32_t count, const uint32_t* err);
   static void check_marks(hipStream_t st, const XY* recs, uint32_t count, uint32_t* err);
@@ -173,6 +179,10 @@ struct CellLaunch {
   // c_m as 32 B big-endian -> coeffs_be (may be null); every cell element range-checked
   static void interp(hipStream_t st, const void* cell_indices, const uint8_t* cells, const uint32_t* rk, uint32_t n,
                      const void* table, void* part, uint32_t* neg_le, uint8_t* coeffs_be, uint32_t* err);
+  // c_m of every cell's own I_k: 8 LE words each in standard form -> coef_le (n x 64 x 8 words), and as
+  // 32 B big-endian -> coeffs_be (may be null); every cell element range-checked
+  static void coeffs(hipStream_t st, const void* cell_indices, const uint8_t* cells, uint32_t n, const void* table,
+                     uint32_t* coef_le, uint8_t* coeffs_be, uint32_t* err);
   // r of the batch -> chal_out (8 big-endian words) and the power table of scalar_prep_pow
   static void batch_challenge(hipStream_t st, const uint8_t* commitments, uint32_t m, const void* commitment_indices,
                               const void* cell_indices, const uint8_t* cells, const uint8_t* proofs, uint32_t n,

@@ -32,6 +32,13 @@ void CellLaunch::interp(hipStream_t st, const void* cell_indices, const uint8_t*
   k_cell_sum<<<1, CELL_N, 0, st>>>((const BlobF*)part, neg_le, coeffs_be);
 }
 
+void CellLaunch::coeffs(hipStream_t st, const void* cell_indices, const uint8_t* cells, uint32_t n, const void* table,
+                        uint32_t* coef_le, uint8_t* coeffs_be, uint32_t* err) {
+  if (n)
+    k_cell_coeffs<<<grid_for(n, CELL_COEFF_PACK), 64 * CELL_COEFF_PACK, 0, st>>>(
+        (const uint64_t*)cell_indices, cells, n, (const BlobF*)table, coef_le, coeffs_be, err);
+}
+
 void CellLaunch::batch_challenge(hipStream_t st, const uint8_t* commitments, uint32_t m, const void* commitment_indices,
                                  const void* cell_indices, const uint8_t* cells, const uint8_t* proofs, uint32_t n,
                                  void* pow, uint32_t* chal_out) {

@@ -9,6 +9,9 @@
 //   r_i pi_i                -> tree A_g, 4-word scalars
 //   r_i C_i, s_i pi_i       -> tree B_g, 4- and 8-word scalars (s_i = r_i z_i mod r)
 //   (-t_g) G1               -> tree B_g, t_g = sum_{i in g} r_i y_i (k_group_tsum)
+// A range of EIP-7594 cells (z_k = h_k^64, y_k = 0) has 3 len + 64 waves: in place of the last term
+//   (-c_m(g)) [tau^m]_1     -> tree B_g, m < 64, c_m(g) = sum_{k in g} r_k coef_k[m] (k_cell_range_fold)
+// over the points [pi (n) | C (n) | tau^m (64)].
 // No GLV split: the sums are the same on G1 and exact off it.  Points: the slot's radix-2^29 slots
 // [pi (n) | C (n) | G1], as k_small_msm reads them.  Results: res[2 g] = A_g, res[2 g + 1] = B_g (XYZZ).
 // The arrival counters are zeroed by every launch (launch_find.hip).
@@ -64,7 +67,43 @@ __global__ void __launch_bounds__(256) k_group_tsum(const FindGroup* __restrict_
   }
 }
 
+// -c_m(g) = -(sum of r_k coef_k[m] over group g's cells) mod r, m < 64, as 8 LE words each at
+// negt[8 (64 g + m)]: the scalars of a cell range's 64 tail terms, in the place of k_group_tsum's one
+// (y_k = 0 for cells).  coef: k_cell_coeffs' table, 64 x 8 LE words per cell in standard form.  One
+// block per group: wave s takes the cells lo + s, lo + s + 4, ... (r_k is wave-uniform), lane m
+// coefficient m, so consecutive lanes read consecutive 32 B; the four strides meet in LDS.
 template <class Cv>
+__global__ void __launch_bounds__(256) k_cell_range_fold(const FindGroup* __restrict__ groups, Seed seed,
+                                                         uint64_t index_offset, const uint32_t* __restrict__ coef,
+                                                         uint32_t* __restrict__ negt) {
+  using R = typename Cv::FrP;
+  using F = Fp<R>;
+  __shared__ F lds[256];
+  const FindGroup g = groups[blockIdx.x];
+  const uint32_t m = threadIdx.x & 63u;
+  F acc = F::zero();
+  for (uint32_t k = threadIdx.x >> 6; k < g.len; k += 4) {
+    const uint32_t i = g.lo + k;
+    uint32_t r4[4];
+    randomizer127(seed.w, index_offset + i, r4);
+    F r = F::zero();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r.v[q] = r4[q];
+    F cf;
+    load_words(reinterpret_cast<const uint8_t*>(coef + 8 * ((size_t)i * 64 + m)), cf.v);
+    acc = fp_add(acc, fp_mul(fp_to_mont(r), cf));  // r c (standard form)
+  }
+  lds[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const F t = fp_neg(fp_add(fp_add(lds[m], lds[64 + m]), fp_add(lds[128 + m], lds[192 + m])));
+    store_words(reinterpret_cast<uint8_t*>(negt + 8 * ((size_t)blockIdx.x * 64 + m)), t.v);
+  }
+}
+
+// T: the group's tail terms (find_plan.hpp): 1 for opening tuples, 64 for cell ranges, whose tail
+// term m reads point pts[2 n + m] and scalar negt[8 (T g + m)] and is leaf 2 len + m of tree B
+template <class Cv, uint32_t T = 1>
 __global__ void __launch_bounds__(64) k_group_msm(GroupBatch b, const FindGroup* __restrict__ groups,
                                                   const Affine<Cv>* __restrict__ pts, const uint8_t* __restrict__ inf,
                                                   uint32_t* __restrict__ nodes, uint32_t* __restrict__ flags,
@@ -85,14 +124,16 @@ __global__ void __launch_bounds__(64) k_group_msm(GroupBatch b, const FindGroup*
   const uint32_t gi = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
   const FindGroup g = groups[gi];
   const uint32_t t = w - g.wave_base;  // the term within the group
-  if (t > 3 * g.len) return;           // (a wave past the last group's terms: the grid is exact, so none)
+  if (t > 3 * g.len + (T - 1)) return;  // (a wave past the last group's terms: the grid is exact, so none)
   // its point, scalar, tree (0: A, 1: B) and leaf
   const uint32_t cls = t < g.len ? 0u : t < 2 * g.len ? 1u : t < 3 * g.len ? 2u : 3u;
   const uint32_t i = g.lo + (t - cls * g.len);  // the tuple (classes 0 .. 2)
-  const uint32_t pi = cls == 0 || cls == 2 ? i : cls == 1 ? b.n + i : 2 * b.n;
+  const uint32_t tm = T == 1 ? 0u : t - 3 * g.len;  // the tail term (class 3)
+  const uint32_t pi = cls == 0 || cls == 2 ? i : cls == 1 ? b.n + i : 2 * b.n + tm;
   const uint32_t m = cls == 0 ? 0u : 1u;
   uint32_t v = cls == 0 ? t : t - g.len;
-  const uint32_t* sw = cls <= 1 ? b.scal_r + 4 * (size_t)i : cls == 2 ? b.scal_s + 8 * (size_t)i : b.negt + 8 * (size_t)gi;
+  const uint32_t* sw = cls <= 1 ? b.scal_r + 4 * (size_t)i : cls == 2 ? b.scal_s + 8 * (size_t)i
+                                                                     : b.negt + 8 * ((size_t)T * gi + tm);
   const uint32_t* slot = reinterpret_cast<const uint32_t*>(pts + pi);
   int32_t one = 0, from29 = 0;  // per-lane limbs of R mod p and R^2 / R29 mod p
 #pragma unroll
@@ -125,7 +166,7 @@ __global__ void __launch_bounds__(64) k_group_msm(GroupBatch b, const FindGroup*
   }
   if (P.inf) acc.inf = true;
   // climb tree m of the group (msm_small.hpp)
-  uint32_t cnt = m ? 2 * g.len + 1 : g.len, node = g.node_base[m], flag = g.flag_base[m];
+  uint32_t cnt = m ? 2 * g.len + T : g.len, node = g.node_base[m], flag = g.flag_base[m];
 #pragma unroll 1
   while (cnt > 1) {
     const uint32_t partner = v ^ 1u;

@@ -178,6 +178,13 @@ def lib():
         "kzgmi_verify_blob_batch_find_invalid_device": ([vp, vp, vp, vp, vp, sz, c.POINTER(c.c_uint64), sz,
                                                          c.POINTER(sz), ip], c.c_int),
         "kzgmi_find_invalid_stats": ([vp, c.POINTER(c.c_uint64)], c.c_int),
+        "kzgmi_cell_coeffs_device": ([vp, vp, vp, sz, vp], c.c_int),
+        "kzgmi_cell_range_partials_device": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, c.c_uint64, u8p,
+                                              c.POINTER(c.c_uint64), sz, vp], c.c_int),
+        "kzgmi_verify_cell_batch_find_invalid": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, u8p, c.POINTER(c.c_uint64), sz,
+                                                  c.POINTER(sz), ip], c.c_int),
+        "kzgmi_verify_cell_batch_find_invalid_device": ([vp, vp, vp, sz, vp, vp, vp, vp, sz, u8p, c.POINTER(c.c_uint64),
+                                                         sz, c.POINTER(sz), ip], c.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -228,6 +235,8 @@ def exported_symbols():
         "kzgmi_batch_check_partials_device", "kzgmi_batch_range_partials_device", "kzgmi_batch_find_invalid",
         "kzgmi_batch_find_invalid_device", "kzgmi_verify_blob_batch_find_invalid",
         "kzgmi_verify_blob_batch_find_invalid_device", "kzgmi_find_invalid_stats",
+        "kzgmi_cell_coeffs_device", "kzgmi_cell_range_partials_device", "kzgmi_verify_cell_batch_find_invalid",
+        "kzgmi_verify_cell_batch_find_invalid_device",
     ]
 
 
@@ -1349,6 +1358,66 @@ class Context:
             del kb, kc, kp
         return list(bad[:nb.value]), bool(more.value)
 
+    def cell_coeffs(self, cell_indices, cells, n: int, out=None):
+        """The 64 coefficients of every cell's own interpolation polynomial I_k, for device-resident
+        uint64 cell indices and cells: a device tensor of n x 64 x 32 B big-endian (diagnostic)."""
+        import torch
+        if out is None:
+            out = torch.empty(max(16, CELL_BYTES * n), dtype=torch.uint8, device=cells.device)[:CELL_BYTES * n]
+        pi, pc, po = _dptr(cell_indices, 8 * n), _dptr(cells, CELL_BYTES * n), _dptr(out, CELL_BYTES * n)
+        self._order(0)
+        _check(lib().kzgmi_cell_coeffs_device(self.handle, pi, pc, int(n), po))
+        return out
+
+    def cell_range_partials(self, srs: CellSrs, commitments, commitment_indices, cell_indices, cells, proofs, m: int,
+                            n: int, index_offset: int, seed, ranges, out):
+        """(A_g, B_g) of the index ranges [(lo, hi), ...] of a device-resident cell batch whose first
+        cell has global index index_offset: 2 partial records per range into the device tensor `out`."""
+        h = self._cell_srs_handle(srs)
+        ptrs = (_dptr(commitments, 48 * m), int(m), _dptr(commitment_indices, 8 * n), _dptr(cell_indices, 8 * n),
+                _dptr(cells, CELL_BYTES * n), _dptr(proofs, 48 * n))
+        flat = [int(v) for r in ranges for v in r]
+        arr = (ctypes.c_uint64 * max(1, len(flat)))(*flat)
+        po = _dptr(out, 2 * len(ranges) * self.partial_bytes("bls12_381"))
+        self._order(0)
+        _check(lib().kzgmi_cell_range_partials_device(self.handle, h, *ptrs, int(n), int(index_offset),
+                                                      _challenge_seed(seed, None), arr, len(ranges), po))
+
+    def cell_batch_find_invalid(self, srs: CellSrs, commitments, commitment_indices, cell_indices, cells, proofs,
+                                m: Optional[int] = None, n: Optional[int] = None, seed: Optional[bytes] = None,
+                                max_bad: int = 64):
+        """The cells verify_cell_batch rejects a batch for, found on the GPU by group testing over
+        index ranges: -> (the lowest min(max_bad, #invalid) invalid indices ascending, more).  Host
+        buffers or device tensors, as verify_cell_batch takes them; at most 65536 cells per call.
+        seed: the 32-byte seed of the counter-mode randomisers (None: the OS CSPRNG)."""
+        bad, nb, more = self._find_outputs(max_bad)
+        h = self._cell_srs_handle(srs)
+        sd = _challenge_seed(seed, None)
+        if _is_device_tensor(cells):
+            if n is None:
+                n = proofs.numel() // 48
+            if m is None:
+                m = commitments.numel() // 48
+            ptrs = (_dptr(commitments, 48 * m), int(m), _dptr(commitment_indices, 8 * n), _dptr(cell_indices, 8 * n),
+                    _dptr(cells, CELL_BYTES * n), _dptr(proofs, 48 * n))
+            self._order(0)
+            _check(lib().kzgmi_verify_cell_batch_find_invalid_device(self.handle, h, *ptrs, int(n), sd, bad, max_bad,
+                                                                     ctypes.byref(nb), ctypes.byref(more)))
+        else:
+            ci, ce = _u64_bytes(commitment_indices), _u64_bytes(cell_indices)
+            (pc, lc, kc), (pi, li, ki), (pe, le, ke), (pl, ll, kl), (pp, lp, kp) = (
+                _host_ptr(v) for v in (commitments, ci, ce, cells, proofs))
+            if n is None:
+                n = lp // 48
+            if m is None:
+                m = lc // 48
+            if lc < 48 * m or li < 8 * n or le < 8 * n or ll < CELL_BYTES * n or lp < 48 * n:
+                raise ValueError("input buffers shorter than n cells")
+            _check(lib().kzgmi_verify_cell_batch_find_invalid(self.handle, h, pc, int(m), pi, pe, pl, pp, int(n), sd, bad,
+                                                              max_bad, ctypes.byref(nb), ctypes.byref(more)))
+            del kc, ki, ke, kl, kp
+        return list(bad[:nb.value]), bool(more.value)
+
     def find_invalid_stats(self) -> dict:
         """Of the last search on this context: levels, bucket_jobs, wave_terms (grouped kernel), pairings."""
         out = (ctypes.c_uint64 * 4)()
@@ -1513,11 +1582,10 @@ def blob_batch_find_invalid(blobs, commitments, proofs, srs: Srs, n: Optional[in
     return srs.ctx.blob_batch_find_invalid(srs, blobs, commitments, proofs, n=n, max_bad=max_bad)
 
 
-def verify_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs: CellSrs, r=None) -> bool:
-    """EIP-7594 verify_cell_kzg_proof_batch(commitments_bytes, cell_indices, cells, proofs_bytes) on
-    the GPU (BLS12-381): lists of 48-byte commitments (one per cell, repeats allowed), cell
-    indices, 2048-byte cells and 48-byte proofs.  Commitments are deduplicated here, in order of
-    first appearance."""
+def _dedup_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs):
+    """The specification's per-cell lists in the deduplicated form Context.verify_cell_batch takes:
+    (unique commitments, commitment indices, cell indices, cells, proofs, m, n); the commitments
+    are deduplicated in order of first appearance."""
     n = len(cells)
     if not (len(commitments_bytes) == len(cell_indices) == len(proofs_bytes) == n):
         raise ValueError("commitments, cell indices, cells and proofs must have the same length")
@@ -1530,8 +1598,24 @@ def verify_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs:
         cidx.append(index[cm])
     if not isinstance(srs, CellSrs):
         raise KzgmiError(-1, "not a cell SRS (Context.load_cell_srs)")
-    return srs.ctx.verify_cell_batch(srs, b"".join(unique), cidx, list(cell_indices), b"".join(bytes(x) for x in cells),
-                                     b"".join(bytes(p) for p in proofs_bytes), m=len(unique), n=n, r=r)
+    return (b"".join(unique), cidx, list(cell_indices), b"".join(bytes(x) for x in cells),
+            b"".join(bytes(p) for p in proofs_bytes), len(unique), n)
+
+
+def verify_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs: CellSrs, r=None) -> bool:
+    """EIP-7594 verify_cell_kzg_proof_batch(commitments_bytes, cell_indices, cells, proofs_bytes) on
+    the GPU (BLS12-381): lists of 48-byte commitments (one per cell, repeats allowed), cell
+    indices, 2048-byte cells and 48-byte proofs.  Commitments are deduplicated here, in order of
+    first appearance."""
+    *args, m, n = _dedup_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs)
+    return srs.ctx.verify_cell_batch(srs, *args, m=m, n=n, r=r)
+
+
+def cell_batch_find_invalid(commitments_bytes, cell_indices, cells, proofs_bytes, srs: CellSrs,
+                            seed: Optional[bytes] = None, max_bad: int = 64):
+    """The cells verify_cell_batch (same arguments) rejects a batch for: -> (indices ascending, more)."""
+    *args, m, n = _dedup_cell_batch(commitments_bytes, cell_indices, cells, proofs_bytes, srs)
+    return srs.ctx.cell_batch_find_invalid(srs, *args, m=m, n=n, seed=seed, max_bad=max_bad)
 
 
 def compute_cells(blobs, n: Optional[int] = None, ctx: Optional[Context] = None):
