@@ -943,19 +943,106 @@ KZ_DEV F29<Q> one_literals(std::integer_sequence<int, K...>) {
 // x < 10p; y < 16p; zz, zzz < 2p; products < 2p -- only two biased multiples of p (8p, 16p),
 // so few constants stay live across the loop.  BN254 (R29 / p ~ 169, no such headroom): q.y <
 // p, x < 5.2p, y < 3.2p, zz, zzz < 1.1p with the biases 1p..8p.  Each subtraction names its
-// bias by role (Q::ACC_*), chosen and checked per curve by tools/gen_params29.py.  ZZ/ZZZ in
-// LDS as in the 32-bit loop below.
-// acc_row29 (row accumulation, below) holds a copy of this loop's helpers, value streaming and
-// addition body on another schedule -- a copy, so that this kernel's code generation is not
-// touched by it: a change to the addition is made at both sites (the stage test of the row path
-// compares the two kernels' records word for word).  Sharing the body is a follow-up that has to
-// clear an A/B of k_accumulate first.  Where the two differ: acc_row29's hot loop negates q.y
-// limb by limb without a carry pass (neg_lazy29), which this loop cannot -- `if (inf)` below
-// copies q.y into the running sum at every bucket start, and the running sum holds normalised
-// values -- and acc_row29 peels an item's first addition (ZZ = ZZZ = ONE: no products by ONE) in
-// front of its loop, where every lane of a row is at that addition at once; here a bucket's
-// first addition is some iteration of the loop, another one in every lane.  The integers, and so
-// the records, are the same.
+// bias by role (Q::ACC_*), chosen and checked per curve by tools/gen_params29.py.  ZZ / ZZZ of
+// the running sum live in LDS columns (s_zz[k][tx]: limb k of thread tx), x and y in registers.
+//
+// acc_loop29 (k_accumulate: equal chunks of entries) and acc_row29 (k_accumulate_rows, below) run
+// the same addition on two schedules.  Defined once, here: the LDS columns, the literal ONE, the
+// record store, the value stream, P and R (madd_pr29), PP, PPP and the column updates (madd_pp29)
+// and the doubling exit.  Each loop owns its schedule, its zero tests of P and R and their
+// branches -- and, still, its load_q and the four lines of the tail (Q2, X3, Y3, x := X3; the
+// peel holds them a third time): as functions these two move the code generation of both kernels
+// (profiles/HISTORY.md, round 10), so a change to either is made at every site; the stage test of
+// the row path compares the two kernels' records word for word.
+// A column is the lane's base pointer &s_zz[0][tx], limb k at [k * 256] (as for dbl_affine29).
+template <class Q>
+KZ_DEV F29<Q> col_ld29(const uint32_t* col) {
+  asm volatile("" ::: "memory");
+  F29<Q> r;
+#pragma unroll
+  for (int k = 0; k < Q::N; ++k) r.v[k] = col[k * 256];
+  return r;
+}
+template <class Q>
+KZ_DEV void col_st29(uint32_t* col, const F29<Q>& v) {
+#pragma unroll
+  for (int k = 0; k < Q::N; ++k) col[k * 256] = v.v[k];
+  asm volatile("" ::: "memory");
+}
+// ONE from literal moves at the point of use: the constant held in VGPRs across the loop was spilled
+template <class Q>
+KZ_DEV void cols_one29(uint32_t* zz, uint32_t* zzz) {
+  const F29<Q> one = one_literals<Q>(std::make_integer_sequence<int, Q::N / 2>{});
+  col_st29<Q>(zz, one);
+  col_st29<Q>(zzz, one);
+}
+// The running sum as the record at d, one coordinate at a time (BLS12-381: 8-B stores, a
+// coordinate is 14 words; BN254: 9 words, 4-B aligned); zz = 0 marks infinity
+template <class Q>
+KZ_DEV void store_sum29(uint32_t* d, const F29<Q>& x, const F29<Q>& y, bool inf, const uint32_t* zz, const uint32_t* zzz) {
+  auto put = [](uint32_t* d, const F29<Q>& a) {
+    if constexpr (Q::N % 2 == 0) {
+      _Pragma("unroll") for (int k = 0; k < Q::N / 2; ++k) reinterpret_cast<uint2*>(d)[k] = make_uint2(a.v[2 * k], a.v[2 * k + 1]);
+    } else {
+      _Pragma("unroll") for (int k = 0; k < Q::N; ++k) d[k] = a.v[k];
+    }
+  };
+  put(d, x);
+  put(d + Q::N, y);
+  put(d + 2 * Q::N, inf ? F29<Q>::zero() : col_ld29<Q>(zz));
+  put(d + 3 * Q::N, col_ld29<Q>(zzz));
+}
+// The value stream: 4 values at a time, one 16-B group fetched a group ahead of its use (each
+// lane walks its own run, so a per-entry 4-B load re-fetched the run's sector from beyond L2 for
+// most entries).  A group lands in LDS by an asynchronous global_load_lds_dwordx4, each lane's
+// 16 B at its wave's s_vq[lane]; no VGPR holds the values across the addition (in registers they
+// were spilled around it: 177.1 vs 179.4 batch-verifies/s, profiles/r04/ab_acc_vq_lds.txt).  With
+// the lane slot from v_mbcnt and ONE from literals the loops have no scratch traffic at all
+// (180.4 vs 179.4/s, profiles/r04/ab_acc_spill_free.txt).
+// vals_fetch29: the aligned group that holds entry e, in front of a loop; vals_next29: entry e's
+// value, and behind a group's last entry the fetch of the next group.
+KZ_DEV void vals_fetch29(const uint32_t* sorted_val, uint32_t e, uint4* s_vq, uint32_t tx) {
+  __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + (e & ~3u)), &s_vq[tx & ~63u], 16, 0, 0);
+}
+KZ_DEV uint32_t vals_next29(const uint32_t* sorted_val, uint32_t e, uint4* s_vq, uint32_t tx) {
+  const uint32_t j = e & 3u;
+  uint32_t lane;  // from v_mbcnt every iteration: a loop-invariant address VGPR was spilled around the addition
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+  const uint32_t v = reinterpret_cast<const uint32_t*>(&s_vq[(tx & ~63u) + lane])[j];
+  if (j == 3) {
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): v is read before the next group lands over it
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + e + 1), &s_vq[tx & ~63u], 16, 0, 0);
+  }
+  return v;
+}
+// P = U2 - X1, R = S2 - Y1: on the products' own high columns (mulsub29: no carry pass) under
+// kFusedSub; BLS12-381 < 18p.  The caller tests them: P = R = 0 is the doubling, P = 0 alone O.
+template <class Cv, class G = F29<Fp29Of<Cv>>>
+KZ_DEV void madd_pr29(const G& qx, const G& qy, const G& x, const G& y, const uint32_t* zz, const uint32_t* zzz, G& P, G& R) {
+  using Q = Fp29Of<Cv>;
+  P = kFusedSub<Cv> ? mulsub29(qx, col_ld29<Q>(zz), x, Q::ACC_P) : sub29(mul29(qx, col_ld29<Q>(zz)), x, Q::ACC_P);
+  R = kFusedSub<Cv> ? mulsub29(qy, col_ld29<Q>(zzz), y, Q::ACC_R) : sub29(mul29(qy, col_ld29<Q>(zzz)), y, Q::ACC_R);
+}
+// PP, PPP and ZZ *= PP, ZZZ *= PPP in the columns
+template <class Q>
+KZ_DEV void madd_pp29(const F29<Q>& P, uint32_t* zz, uint32_t* zzz, F29<Q>& PP, F29<Q>& PPP) {
+  PP = sqr29(P);
+  PPP = mul29(P, PP);
+  col_st29<Q>(zz, mul29(col_ld29<Q>(zz), PP));
+  col_st29<Q>(zzz, mul29(col_ld29<Q>(zzz), PPP));
+}
+// The rare doubling (running sum == incoming point q) leaves the hot loops: a call or the
+// doubling's temporaries inside them would raise the loop's register peak (a call there cost
+// ~48 spilled VGPRs at 4 waves); the outer loop does it here and resumes at the next entry.
+template <class Q>
+KZ_DEV void dbl_entry29(const F29<Q>& qx, const F29<Q>& qy, uint32_t* zz, uint32_t* zzz, F29<Q>& x, F29<Q>& y) {
+  asm volatile("" ::: "memory");
+  const Xy29<Q> d = dbl_affine29<Q>(qx, qy, zz, zzz);
+  asm volatile("" ::: "memory");
+  x = d.x;
+  y = d.y;
+}
+
 template <class Cv>
 KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t chunk, uint32_t cur,
                        const uint32_t* __restrict__ sorted_val, const uint32_t* __restrict__ sorted_key,
@@ -963,27 +1050,16 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
                        uint32_t nthreads) {
   using Q = Fp29Of<Cv>;
   using G = F29<Q>;
-  constexpr int N = Q::N, W29 = kW29<Q>;
-  __shared__ uint32_t s_zz[N][256], s_zzz[N][256];
+  constexpr int W29 = kW29<Q>;
+  __shared__ uint32_t s_zz[Q::N][256], s_zzz[Q::N][256];
+  __shared__ uint4 s_vq[256];
   const uint32_t tx = threadIdx.x;
-  auto ld = [tx](uint32_t (&a)[N][256]) {
-    asm volatile("" ::: "memory");
-    G r;
-    _Pragma("unroll") for (int k = 0; k < N; ++k) r.v[k] = a[k][tx];
-    return r;
-  };
-  auto st = [tx](uint32_t (&a)[N][256], const G& v) {
-    _Pragma("unroll") for (int k = 0; k < N; ++k) a[k][tx] = v.v[k];
-    asm volatile("" ::: "memory");
-  };
-  // one coordinate at a time (BLS12-381: 8-B stores, a coordinate is 14 words; BN254: 9 words,
-  // 4-B aligned), zz = 0 marks infinity
-  auto put = [](uint32_t* d, const G& a) {
-    if constexpr (N % 2 == 0) {
-      _Pragma("unroll") for (int k = 0; k < N / 2; ++k) reinterpret_cast<uint2*>(d)[k] = make_uint2(a.v[2 * k], a.v[2 * k + 1]);
-    } else {
-      _Pragma("unroll") for (int k = 0; k < N; ++k) d[k] = a.v[k];
-    }
+  uint32_t* const zz = &s_zz[0][tx];  // the lane's columns: limb k at [k * 256]
+  uint32_t* const zzz = &s_zzz[0][tx];
+  // loads entry e's point (sign applied: -y as ACC_NEG - y; BLS12-381 8p - y)
+  auto load_q = [&](uint32_t v, G& qx, G& qy) {
+    load_pt29<Cv>(reinterpret_cast<const Affine<Cv>*>(pts29) + sv_point(v), qx, qy);
+    if (v & 1) qy = sub29(G::zero(), qy, Q::ACC_NEG);
   };
   // Where a finished bucket goes: only the chunk's first bucket can have started in an earlier
   // chunk (first piece) and only its last can continue into a later one (last piece), so both
@@ -994,48 +1070,18 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
   auto flush = [&](const G& x, const G& y, uint32_t key, bool inf, bool ends_after) {
     const size_t rec = (first && started_before) ? (size_t)nb + chunk : ends_after ? (size_t)nb + nthreads + chunk : key;
     first = false;
-    uint32_t* d = acc29 + rec * W29;
-    put(d, x);
-    put(d + N, y);
-    put(d + 2 * N, inf ? G::zero() : ld(s_zz));
-    put(d + 3 * N, ld(s_zzz));
+    store_sum29<Q>(acc29 + rec * W29, x, y, inf, zz, zzz);
   };
   G x = G::zero(), y = G::zero();
   bool inf = true;  // running sum = O: at every bucket start, and after P + (-P)
-  // loads entry e's point (sign applied: -y as ACC_NEG - y; BLS12-381 8p - y)
-  auto load_q = [&](uint32_t v, G& qx, G& qy) {
-    load_pt29<Cv>(reinterpret_cast<const Affine<Cv>*>(pts29) + sv_point(v), qx, qy);
-    if (v & 1) qy = sub29(G::zero(), qy, Q::ACC_NEG);
-  };
-  // The rare doubling (running sum == incoming point) leaves the hot loop: a call or the
-  // doubling's temporaries inside it would raise the loop's register peak (a call there cost
-  // ~48 spilled VGPRs at 4 waves); the outer loop does it and resumes at the next entry.
   uint32_t e = start;
   for (;;) {
     bool dbl = false;
-    // The values stream 4 at a time (one 16-B load per 4 entries, issued an iteration ahead of
-    // their use; chunks start 16-B aligned, acc_chunk_len): each lane walks its own run, so a
-    // per-entry 4-B load re-fetched the run's sector from beyond L2 for most entries.  A bucket
-    // change is the SV_FIRST bit of the value; the key is read only then (a flush).
-    // (The 4 values in registers were spilled to scratch and back around the addition at 128
-    // VGPRs: 177.1 vs 179.4 batch-verifies/s, profiles/r04/ab_acc_vq_lds.txt.)  The 4 values of a group land in LDS by an asynchronous global_load_lds_dwordx4, one group
-    // ahead; no VGPR holds them across the addition.  With the lane slot from v_mbcnt and ONE
-    // from literals (below) the loop has no scratch traffic at all and needs 123 VGPRs (180.4 vs
-    // 179.4/s, profiles/r04/ab_acc_spill_free.txt).
-    __shared__ uint4 s_vq[256];
-    uint4* const vq_wave = &s_vq[tx & ~63u];  // each lane's 16 B land at vq_wave[lane]
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + (e & ~3u)), vq_wave, 16, 0, 0);
+    // chunks start 16-B aligned (acc_chunk_len).  A bucket change is the SV_FIRST bit of the
+    // value; the key is read only then (a flush).
+    vals_fetch29(sorted_val, e, s_vq, tx);
     for (; e < end; ++e) {
-      const uint32_t j = e & 3u;
-      // the lane's slot from v_mbcnt every iteration: a loop-invariant address VGPR was spilled
-      // and reloaded from scratch around the addition
-      uint32_t lane;
-      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-      const uint32_t v = reinterpret_cast<const uint32_t*>(&s_vq[(tx & ~63u) + lane])[j];
-      if (j == 3) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): v is read before the next group lands over it
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + e + 1), vq_wave, 16, 0, 0);
-      }
+      const uint32_t v = vals_next29(sorted_val, e, s_vq, tx);
       if ((v & SV_FIRST) && e != start) {
         flush(x, y, cur, inf, false);
         inf = true;
@@ -1046,17 +1092,12 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
       if (inf) {
         x = qx;
         y = qy;
-        {  // ONE from literal moves here: the constant held in VGPRs across the loop was spilled
-          const G one = one_literals<Q>(std::make_integer_sequence<int, N / 2>{});
-          st(s_zz, one);
-          st(s_zzz, one);
-        }
+        cols_one29<Q>(zz, zzz);
         inf = false;
         continue;
       }
-      // U2 - X1 and S2 - Y1 ride on the products' own high columns (mulsub29: no carry pass)
-      const G P = kFusedSub<Cv> ? mulsub29(qx, ld(s_zz), x, Q::ACC_P) : sub29(mul29(qx, ld(s_zz)), x, Q::ACC_P);  // BLS12-381 < 18p
-      const G R = kFusedSub<Cv> ? mulsub29(qy, ld(s_zzz), y, Q::ACC_R) : sub29(mul29(qy, ld(s_zzz)), y, Q::ACC_R);  // BLS12-381 < 18p
+      G P, R, PP, PPP;
+      madd_pr29<Cv>(qx, qy, x, y, zz, zzz, P, R);
       if (is_zero29_mf(P)) {
         if (is_zero29_mf(R)) {
           dbl = true;
@@ -1065,10 +1106,7 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
         inf = true;
         continue;
       }
-      const G PP = sqr29(P);
-      const G PPP = mul29(P, PP);
-      st(s_zz, mul29(ld(s_zz), PP));
-      st(s_zzz, mul29(ld(s_zzz), PPP));
+      madd_pp29<Q>(P, zz, zzz, PP, PPP);
       const G Q2 = mul29(x, PP);
       // R^2 - PPP - 2 Q2, the subtraction in the square's high columns; BLS12-381 < 10p
       const G X3 = kFusedSub<Cv> ? sqrsub3_29(R, PPP, Q2, Q::ACC_X3) : sub3_29(sqr29(R), PPP, Q2, Q::ACC_X3);
@@ -1079,11 +1117,7 @@ KZ_DEV void acc_loop29(uint32_t start, uint32_t end, uint32_t total, uint32_t ch
     if (!dbl) break;
     G qx, qy;  // entry e: running sum := 2 q
     load_q(sorted_val[e], qx, qy);
-    asm volatile("" ::: "memory");
-    const Xy29<Q> d = dbl_affine29<Q>(qx, qy, &s_zz[0][tx], &s_zzz[0][tx]);
-    asm volatile("" ::: "memory");
-    x = d.x;
-    y = d.y;
+    dbl_entry29<Q>(qx, qy, zz, zzz, x, y);
     ++e;
   }
   flush(x, y, cur, inf, end < total && sorted_key[end] == cur);
@@ -1400,51 +1434,31 @@ static __global__ void __launch_bounds__(256) k_items_scatter(const uint32_t* __
   }
 }
 
-// One item: the sum of the entries [first, first + len) into record rec.  The mixed addition, its
-// biases and bounds, ZZ / ZZZ in the LDS columns and the value groups in LDS are those of
-// acc_loop29 above; what differs is the schedule.  The first entry is copied in front of the loop
-// (every live lane of the row at once), the loop body never flushes, and the one record is stored
-// behind it.  Values: the aligned 16-B group that holds the entry, as acc_loop29 reads them (an
-// item starts on any 4-B boundary; the lanes of a row then fetch their next group in different
-// iterations of four, a masked issue of one load each).
-// The lambdas, the value streaming and the addition body are copied from acc_loop29, not shared with
-// it (see the note there): keep the two in step.  Two differences, which leave every record word
-// for word what it was.  An item's first addition is peeled in front of the loop without its four
-// products by ONE (kPeelFirst, at its place below).  And the hot loop negates q.y lazily
-// (neg_lazy29: ACC_NEG - q.y limb by limb, 1
-// VALU per limb instead of sub29's carry pass).  There q.y is only an operand of R = q.y ZZZ - y,
-// and a product returns the words of the integer however its limbs carry it (column bound and top
-// limb: tools/gen_params29.py check_bounds, both curves).  Here a lane's y is never a copy of the
-// loop's q.y unnormalised: the first entry is loaded in front of the loop and the doubling's
-// entry behind it, both with sub29, and the restart after P + (-P) -- rare, per lane -- runs the
-// carry pass on the lazy form (norm29: the words of sub29).  acc_loop29 copies q.y into the
-// running sum at every bucket start of every lane, inside the loop, so it keeps sub29.
+// One item: the sum of the entries [first, first + len) into record rec, with the shared pieces
+// above acc_loop29 on another schedule.  The first entry is copied in front of the loop (every
+// live lane of the row at once), the loop body never flushes, and the one record is stored behind
+// it.  An item starts on any 4-B boundary; the lanes of a row then fetch their next value group
+// in different iterations of four, a masked issue of one load each.
+// Two things are this schedule's own, and leave every record word for word what acc_loop29
+// stores.  An item's first addition is peeled without its four products by ONE (kPeelFirst, at
+// its place below).  And the hot loop negates q.y lazily (neg_lazy29, 1 VALU per limb instead of
+// sub29's carry pass): there q.y is only an operand of R = q.y ZZZ - y, and a product returns the
+// words of the integer however its limbs carry it (column bound and top limb: tools/
+// gen_params29.py check_bounds, both curves).  A lane's y is never a copy of the loop's q.y
+// unnormalised: the first entry and the doubling's entry are loaded with sub29, and the restart
+// after P + (-P) -- rare, per lane -- runs the carry pass on the lazy form (norm29: the words of
+// sub29).  acc_loop29 copies q.y into the running sum at every bucket start, so it keeps sub29.
 template <class Cv>
 KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t* __restrict__ sorted_val,
                       const uint32_t* __restrict__ pts29, uint32_t* __restrict__ acc29) {
   using Q = Fp29Of<Cv>;
   using G = F29<Q>;
-  constexpr int N = Q::N, W29 = kW29<Q>;
-  __shared__ uint32_t s_zz[N][256], s_zzz[N][256];
+  constexpr int W29 = kW29<Q>;
+  __shared__ uint32_t s_zz[Q::N][256], s_zzz[Q::N][256];
   __shared__ uint4 s_vq[256];
   const uint32_t tx = threadIdx.x;
-  auto ld = [tx](uint32_t (&a)[N][256]) {
-    asm volatile("" ::: "memory");
-    G r;
-    _Pragma("unroll") for (int k = 0; k < N; ++k) r.v[k] = a[k][tx];
-    return r;
-  };
-  auto st = [tx](uint32_t (&a)[N][256], const G& v) {
-    _Pragma("unroll") for (int k = 0; k < N; ++k) a[k][tx] = v.v[k];
-    asm volatile("" ::: "memory");
-  };
-  auto put = [](uint32_t* d, const G& a) {
-    if constexpr (N % 2 == 0) {
-      _Pragma("unroll") for (int k = 0; k < N / 2; ++k) reinterpret_cast<uint2*>(d)[k] = make_uint2(a.v[2 * k], a.v[2 * k + 1]);
-    } else {
-      _Pragma("unroll") for (int k = 0; k < N; ++k) d[k] = a.v[k];
-    }
-  };
+  uint32_t* const zz = &s_zz[0][tx];  // the lane's columns: limb k at [k * 256]
+  uint32_t* const zzz = &s_zzz[0][tx];
   // lazy (compile-time at each call site): -y as ACC_NEG - y limb by limb, for the hot loop only
   auto load_q = [&](uint32_t v, G& qx, G& qy, auto lazy) {
     load_pt29<Cv>(reinterpret_cast<const Affine<Cv>*>(pts29) + sv_point(v), qx, qy);
@@ -1455,12 +1469,6 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
   };
   constexpr std::false_type normalised{};
   constexpr std::true_type lazy_neg{};
-  auto set_one = [&]() {  // ONE from literal moves (acc_loop29)
-    const G one = one_literals<Q>(std::make_integer_sequence<int, N / 2>{});
-    st(s_zz, one);
-    st(s_zzz, one);
-  };
-  uint4* const vq_wave = &s_vq[tx & ~63u];  // each lane's 16 B land at vq_wave[lane]
   const uint32_t end = first + len;
   uint32_t e = first;
   G x, y;
@@ -1491,12 +1499,12 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
       R = sub29(S2, y, Q::ACC_R);
       ok &= !is_zero29_mf(P);
       PP = sqr29(P);
-      const G zz = canon29(PP);
-      st(s_zz, zz);
+      const G ZZ3 = canon29(PP);
+      col_st29<Q>(zz, ZZ3);
       PPP = mul29(P, PP);
-      const G zzz = canon29(PPP);
-      st(s_zzz, zzz);
-      ok &= peel_ok29(zz) & peel_ok29(zzz);
+      const G ZZZ3 = canon29(PPP);
+      col_st29<Q>(zzz, ZZZ3);
+      ok &= peel_ok29(ZZ3) & peel_ok29(ZZZ3);
     }
     if (__ballot(two && !ok) == 0) {
       if (two) {
@@ -1509,30 +1517,23 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
       }
     }
   }
-  if (one) set_one();
+  if (one) cols_one29<Q>(zz, zzz);
   for (;;) {
     bool dbl = false;
-    __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + (e & ~3u)), vq_wave, 16, 0, 0);
+    vals_fetch29(sorted_val, e, s_vq, tx);
     for (; e < end; ++e) {
-      const uint32_t j = e & 3u;
-      uint32_t lane;
-      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-      const uint32_t v = reinterpret_cast<const uint32_t*>(&s_vq[(tx & ~63u) + lane])[j];
-      if (j == 3) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): v is read before the next group lands over it
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(sorted_val + e + 1), vq_wave, 16, 0, 0);
-      }
+      const uint32_t v = vals_next29(sorted_val, e, s_vq, tx);
       G qx, qy;
       load_q(v, qx, qy, lazy_neg);  // q.y: an operand of R's product only
       if (inf) {  // after P + (-P): this entry starts the sum again (rare, per lane)
         x = qx;
         y = norm29(qy);  // the running sum holds normalised values
-        set_one();
+        cols_one29<Q>(zz, zzz);
         inf = false;
         continue;
       }
-      const G P = kFusedSub<Cv> ? mulsub29(qx, ld(s_zz), x, Q::ACC_P) : sub29(mul29(qx, ld(s_zz)), x, Q::ACC_P);
-      const G R = kFusedSub<Cv> ? mulsub29(qy, ld(s_zzz), y, Q::ACC_R) : sub29(mul29(qy, ld(s_zzz)), y, Q::ACC_R);
+      G P, R, PP, PPP;
+      madd_pr29<Cv>(qx, qy, x, y, zz, zzz, P, R);
       if (is_zero29_mf(P)) {
         if (is_zero29_mf(R)) {
           dbl = true;
@@ -1541,10 +1542,7 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
         inf = true;
         continue;
       }
-      const G PP = sqr29(P);
-      const G PPP = mul29(P, PP);
-      st(s_zz, mul29(ld(s_zz), PP));
-      st(s_zzz, mul29(ld(s_zzz), PPP));
+      madd_pp29<Q>(P, zz, zzz, PP, PPP);
       const G Q2 = mul29(x, PP);
       const G X3 = kFusedSub<Cv> ? sqrsub3_29(R, PPP, Q2, Q::ACC_X3) : sub3_29(sqr29(R), PPP, Q2, Q::ACC_X3);
       y = mul2_29(R, sub29(Q2, X3, Q::ACC_QX), y, neg_lazy29(PPP, Q::ACC_PPP));
@@ -1553,18 +1551,10 @@ KZ_DEV void acc_row29(uint32_t first, uint32_t len, uint32_t rec, const uint32_t
     if (!dbl) break;
     G qx, qy;  // entry e: running sum := 2 q (out of the hot loop, as in acc_loop29)
     load_q(sorted_val[e], qx, qy, normalised);
-    asm volatile("" ::: "memory");
-    const Xy29<Q> d = dbl_affine29<Q>(qx, qy, &s_zz[0][tx], &s_zzz[0][tx]);
-    asm volatile("" ::: "memory");
-    x = d.x;
-    y = d.y;
+    dbl_entry29<Q>(qx, qy, zz, zzz, x, y);
     ++e;
   }
-  uint32_t* d = acc29 + (size_t)rec * W29;
-  put(d, x);
-  put(d + N, y);
-  put(d + 2 * N, inf ? G::zero() : ld(s_zz));  // zz = 0 marks infinity
-  put(d + 3 * N, ld(s_zzz));
+  store_sum29<Q>(acc29 + (size_t)rec * W29, x, y, inf, zz, zzz);
 }
 
 // the launch shape of k_accumulate (one resident round); every wave takes rows of 64 consecutive
