@@ -71,7 +71,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * kzgmi_compute_blob_proofs*, kzgmi_blob_quotient_device, and the search entry points
  * kzgmi_batch_check_partials_device, kzgmi_batch_range_partials_device, kzgmi_batch_find_invalid*,
  * kzgmi_verify_blob_batch_find_invalid*, kzgmi_find_invalid_stats, and the cell search entry points
- * kzgmi_cell_coeffs_device, kzgmi_cell_range_partials_device, kzgmi_verify_cell_batch_find_invalid*.
+ * kzgmi_cell_coeffs_device, kzgmi_cell_range_partials_device, kzgmi_verify_cell_batch_find_invalid*,
+ * and the opening entry points kzgmi_open*, kzgmi_open_quotient_device.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -677,6 +678,40 @@ int kzgmi_commit_device(kzgmi_ctx* ctx, const kzgmi_ck* ck, const void* d_coeffs
 /* Pipelined form: enqueue on workspace `slot`; kzgmi_msm_wait(ctx, slot, out) returns the
  * commitment (G1 encoding). */
 int kzgmi_commit_device_async(kzgmi_ctx* ctx, const kzgmi_ck* ck, int slot, const void* d_coeffs, size_t m);
+
+/* ---- KZG opening proofs over a commit key -- both curves, coefficient form.
+ * For p(X) = sum_{i<m} c_i X^i (m <= the key's n) and k points z_0 .. z_{k-1}:
+ *     y_j = p(z_j),   q_j = (p - y_j) / (X - z_j)  (degree m - 2),   proof_j = [q_j(tau)]_1 = sum_{i<m-1} q_j[i] [tau^i]_1
+ * With Q_m = 0 and Q_i = c_i + z_j Q_{i+1}: y_j = Q_0 and q_j[i-1] = Q_i, 1 <= i < m -- one suffix
+ * scan on the device gives the evaluation and every quotient coefficient; each quotient then takes
+ * kzgmi_commit's MSM over the key.
+ * coeffs: m x 32 B and zs: k x 32 B big-endian canonical Fr (a value >= r: KZGMI_ERR_SCALAR).
+ * ys_out: k x 32 B big-endian.  proofs_out: k uncompressed G1 encodings of the key's curve (96 B / 64 B:
+ * kzgmi_commit's output format and kzgmi_batch_verify's default input; the point at infinity as
+ * everywhere in this header).  m == 0: y = 0, m == 1: y = c_0, and the proof is the point at infinity
+ * in both; k == 0 succeeds and writes nothing.  Points may repeat and may be roots of p (coefficient
+ * form has no special case).  m > n, k > 4096, or a key of another context: KZGMI_ERR_ARG.  The key
+ * lives on the context's primary device and works with that device's slots only.  Device arrays are
+ * 16-byte aligned; outputs overlap neither the inputs nor each other.  The host form stages through
+ * slot 0 and copies the results back; the synchronous device form runs on slot 0; the async form runs
+ * on any slot and completes with kzgmi_slot_wait (ok_out = 1), which reports the device-side errors.
+ * A call that fails writes no output and leaves its slot usable.  Scratch lives in the slot's workspace
+ * (grown on first use, counted by kzgmi_alloc_count) and is bounded: the points are taken in groups
+ * whose quotients hold at most 2^23 scalars (256 MiB; at least one point per group), so a 2^26-term
+ * polynomial opened at 4096 points does not allocate k m 32 B.  (KZGMI_OPEN_GROUP, read at context
+ * creation, sets that bound in scalars: tests.) */
+int kzgmi_open(kzgmi_ctx* ctx, const kzgmi_ck* ck, const uint8_t* coeffs, size_t m, const uint8_t* zs, size_t k,
+               uint8_t* ys_out, uint8_t* proofs_out);
+int kzgmi_open_device(kzgmi_ctx* ctx, const kzgmi_ck* ck, const void* d_coeffs, size_t m, const void* d_zs, size_t k,
+                      void* d_ys_out, void* d_proofs_out);
+int kzgmi_open_device_async(kzgmi_ctx* ctx, const kzgmi_ck* ck, int slot, const void* d_coeffs, size_t m,
+                            const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out);
+/* Diagnostic (synchronous, slot 0, no key; m <= 2^26): y_j -> d_ys_out (k x 32 B) and Q_1 .. Q_{m-1} of
+ * point j -> d_q_out at byte 32 ((m - 1) j + i - 1) for Q_i, big-endian.  Like kzgmi_blob_quotient_device
+ * it writes straight to the caller's arrays, which it does not check for overlap: on an error (a
+ * coefficient or z >= r) their contents are unspecified. */
+int kzgmi_open_quotient_device(kzgmi_ctx* ctx, kzgmi_curve curve, const void* d_coeffs, size_t m, const void* d_zs,
+                               size_t k, void* d_ys_out, void* d_q_out);
 
 /* Optimal-ate pairing e(P, Q) for P in G1, Q in G2: 12 Fp values in tower order, big-endian:
  * 576 B (BLS12-381) / 384 B (BN254).  Test/diagnostic utility.  (ABI 2 returned e(P, Q)^3 on

@@ -252,6 +252,7 @@ int kzgmi_ctx_create_device(kzgmi_ctx** out, int device_id, int pipeline_slots) 
   if (const char* e = getenv("KZGMI_SPLIT_REV")) c->tune.split_rev = atoi(e) != 0;
   if (const char* e = getenv("KZGMI_BLOB_HASH"))
     c->blob_hash = !strcmp(e, "lane") ? BlobLaunch::HASH_LANE : !strcmp(e, "wave") ? BlobLaunch::HASH_WAVE : 0;
+  if (const char* e = getenv("KZGMI_OPEN_GROUP")) c->open_group = std::max<size_t>(1, strtoull(e, nullptr, 10));
   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless set before the runtime
   // starts) and serialises the streams of one queue, so every slot in flight needs a queue of its
   // own (16 slots on 24 queues pipeline; 24 on 24 ran 3.6x slower).  The runtime keeps that many

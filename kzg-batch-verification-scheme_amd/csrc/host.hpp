@@ -106,6 +106,8 @@ struct Slot {
   DevBuf rec_z;                                  // recover_cells: the call's vanishing-polynomial table (recover.hpp)
   DevBuf fk_coef, fk_scal, fk_a, fk_b, fk_enc;   // cell proofs (fk20.hpp): coefficients, ahat, two point vectors, encodings
   DevBuf bp_q, bp_part, bp_enc;                  // blob proofs (blobproof.hpp): quotients, partial sums and results, encodings
+  DevBuf open_zp, open_q, open_aux;              // openings (open.hpp): the points' powers, a group's quotients, run and tile values
+  DevBuf open_y, open_rec, open_enc;             // ... the evaluations, the proofs as records, their encodings
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -137,6 +139,7 @@ struct Slot {
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
                       &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &cell_tab, &rec_z,
                       &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc,
+                      &open_zp, &open_q, &open_aux, &open_y, &open_rec, &open_enc,
                       &find_tab, &find_negt, &find_nodes, &find_flags, &find_rec, &find_ok};
     for (DevBuf* b : bufs) f(*b);
   }
@@ -209,6 +212,9 @@ struct kzgmi_ctx {
   bool blob_table_ready = false;
   // KZGMI_BLOB_HASH=lane|wave forces the blob hash's mapping (A/B, tools/bench_blobs.py); 0: blob_mapping()
   int blob_hash = 0;
+  // Openings (host_open.hip): the points of a call are taken in groups whose quotients hold at most this
+  // many scalars (256 MiB), at least one point per group.  KZGMI_OPEN_GROUP (tests: groups at small sizes)
+  size_t open_group = size_t(1) << 23;
   // EIP-7594 cell front end (cell.hpp): the coset table, built at the first cell call
   DevBuf cell_table;
   bool cell_table_ready = false;

@@ -134,6 +134,17 @@ struct Launch {
   static void check_marks(hipStream_t st, const XY* recs, uint32_t count, uint32_t* err);
   // ---- prover commit key (launch_gen.hip): row out = 2^16 * row in, affine
   static void shift_points(hipStream_t st, const AF* in, const uint8_t* inf_in, uint32_t n, AF* out, uint8_t* inf_out);
+  // ---- KZG openings in coefficient form (open.hpp, launch_open.hip)
+  static uint32_t open_tiles(size_t m);  // tiles of m coefficients
+  // k points (32 B big-endian; >= r raises DERR_SCALAR) -> zp: open_power_bytes() each
+  static size_t open_power_bytes();
+  static void open_points(hipStream_t st, const uint8_t* zs, uint32_t k, uint32_t* zp, uint32_t* err);
+  // The scan of m >= 1 coefficients (8 LE words each, canonical) at the g points whose powers start at
+  // zp: y -> ys (g x 32 B big-endian) and, for m >= 2, Q_1 .. Q_{m-1} of point p -> q + 32 (m - 1) p
+  // bytes, 8 LE words each (be: 32 big-endian bytes).  Scratch, 32 B per value: runv g x tiles x 256,
+  // tilev and tilec g x tiles
+  static void open_quotients(hipStream_t st, const uint32_t* coef, uint32_t m, const uint32_t* zp, uint32_t g, uint32_t* runv,
+                        uint32_t* tilev, uint32_t* tilec, uint8_t* ys, void* q, bool be);
   // ---- generators (launch_gen.hip)
   static void gen_table(hipStream_t st, XY* base, AF* table);
   static void gen_g1(hipStream_t st, const uint8_t* scalars, uint32_t n, const AF* table, uint8_t* out, uint32_t* err);

@@ -93,6 +93,10 @@ def lib():
         "kzgmi_ck_free": ([vp], None),
         "kzgmi_commit": ([vp, vp, u8p, sz, u8p], c.c_int),
         "kzgmi_commit_device": ([vp, vp, vp, sz, u8p], c.c_int),
+        "kzgmi_open": ([vp, vp, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_open_device": ([vp, vp, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_open_device_async": ([vp, vp, c.c_int, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_open_quotient_device": ([vp, c.c_int, vp, sz, vp, sz, vp, vp], c.c_int),
         "kzgmi_fs_challenge_device": ([vp, c.c_int, vp, vp, vp, vp, sz, c.c_uint32, u8p], c.c_int),
         "kzgmi_fs_chunk_digests_device": ([vp, c.c_int, vp, vp, vp, vp, sz, c.c_uint64, c.c_uint32, vp], c.c_int),
         "kzgmi_fs_challenge_from_digests_device": ([vp, c.c_int, vp, sz, c.c_uint64, u8p], c.c_int),
@@ -237,6 +241,7 @@ def exported_symbols():
         "kzgmi_verify_blob_batch_find_invalid_device", "kzgmi_find_invalid_stats",
         "kzgmi_cell_coeffs_device", "kzgmi_cell_range_partials_device", "kzgmi_verify_cell_batch_find_invalid",
         "kzgmi_verify_cell_batch_find_invalid_device",
+        "kzgmi_open", "kzgmi_open_device", "kzgmi_open_device_async", "kzgmi_open_quotient_device",
     ]
 
 
@@ -712,6 +717,65 @@ class Context:
                 m = len(cb) // 32
             _check(lib().kzgmi_commit(self.handle, ck.handle, cb, m, out))
         return out.raw
+
+    # ------------------------------------------------------------------ prover openings
+    def open(self, ck: CommitKey, coeffs, zs, m: Optional[int] = None, k: Optional[int] = None, ys_out=None, out=None):
+        """KZG openings of p = sum_i coeff_i X^i (m <= ck.n coefficients, 32 B canonical Fr each) at the
+        k points zs (32 B each): (proofs, ys) -- k uncompressed G1 encodings [q_j(tau)]_1 of
+        q_j = (p - y_j) / (X - z_j), and k x 32 B evaluations y_j = p(z_j).  Device tensors in: device
+        tensors out (`out`, `ys_out` where given); host buffers in: bytes out."""
+        gb = 2 * FP_BYTES[ck.curve]
+        if _is_device_tensor(zs):
+            import torch
+            if m is None:
+                m = coeffs.numel() * coeffs.element_size() // 32
+            if k is None:
+                k = zs.numel() * zs.element_size() // 32
+            if out is None:
+                out = torch.empty(max(1, k) * gb, dtype=torch.uint8, device=zs.device)[:k * gb]
+            if ys_out is None:
+                ys_out = torch.empty(max(1, k) * 32, dtype=torch.uint8, device=zs.device)[:k * 32]
+            pc = _dptr(coeffs, 32 * m) if m else None
+            ptrs = (pc, int(m), _dptr(zs, 32 * k), int(k), _dptr(ys_out, 32 * k), _dptr(out, gb * k))
+            self._order(0)
+            _check(lib().kzgmi_open_device(self.handle, ck.handle, *ptrs))
+            return out, ys_out
+        hc, hz = _host_ptr(coeffs), _host_ptr(zs)
+        if m is None:
+            m = hc[1] // 32
+        if k is None:
+            k = hz[1] // 32
+        if hc[1] < 32 * m or hz[1] < 32 * k:
+            raise ValueError("input buffers shorter than m coefficients / k points")
+        pb, yb = ctypes.create_string_buffer(max(1, k * gb)), ctypes.create_string_buffer(max(1, k * 32))
+        _check(lib().kzgmi_open(self.handle, ck.handle, hc[0] or None, int(m), hz[0] or None, int(k),
+                                ctypes.addressof(yb), ctypes.addressof(pb)))
+        del hc, hz
+        return pb.raw[:k * gb], yb.raw[:k * 32]
+
+    def open_async(self, ck: CommitKey, slot: int, coeffs, zs, m: int, k: int, ys_out, out):
+        """Enqueue open() of device tensors on `slot`; wait(slot) completes it (and raises its
+        device-side errors)."""
+        gb = 2 * FP_BYTES[ck.curve]
+        ptrs = (_dptr(coeffs, 32 * m) if m else None, int(m), _dptr(zs, 32 * k), int(k), _dptr(ys_out, 32 * k),
+                _dptr(out, gb * k))
+        self._order(slot)
+        _check(lib().kzgmi_open_device_async(self.handle, ck.handle, int(slot), *ptrs))
+
+    def open_quotient(self, curve: str, coeffs, m: int, zs, k: int, ys_out=None, out=None):
+        """Diagnostic: (ys, q) of m device-resident coefficients at k device-resident points: y_j = p(z_j)
+        (k x 32 B) and the m - 1 coefficients of (p - y_j) / (X - z_j), lowest first (k x (m - 1) x 32 B)."""
+        import torch
+        nq = max(m - 1, 0)
+        if ys_out is None:
+            ys_out = torch.empty(max(1, k) * 32, dtype=torch.uint8, device=zs.device)[:32 * k]
+        if out is None:
+            out = torch.empty(max(1, k * nq) * 32, dtype=torch.uint8, device=zs.device)[:32 * k * nq]
+        ptrs = (_dptr(coeffs, 32 * m) if m else None, int(m), _dptr(zs, 32 * k), int(k), _dptr(ys_out, 32 * k),
+                _dptr(out, 32 * k * nq))
+        self._order(0)
+        _check(lib().kzgmi_open_quotient_device(self.handle, CURVES[curve], *ptrs))
+        return ys_out, out
 
     # ------------------------------------------------------------------ Fiat-Shamir
     def commit_async(self, ck: CommitKey, slot: int, coeffs, m: int):
