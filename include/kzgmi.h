@@ -72,7 +72,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * kzgmi_batch_check_partials_device, kzgmi_batch_range_partials_device, kzgmi_batch_find_invalid*,
  * kzgmi_verify_blob_batch_find_invalid*, kzgmi_find_invalid_stats, and the cell search entry points
  * kzgmi_cell_coeffs_device, kzgmi_cell_range_partials_device, kzgmi_verify_cell_batch_find_invalid*,
- * and the opening entry points kzgmi_open*, kzgmi_open_quotient_device.
+ * and the opening entry points kzgmi_open*, kzgmi_open_quotient_device, and the transform entry points
+ * kzgmi_fr_ntt* with the evaluation-form openings kzgmi_open_evals*.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -712,6 +713,56 @@ int kzgmi_open_device_async(kzgmi_ctx* ctx, const kzgmi_ck* ck, int slot, const 
  * coefficient or z >= r) their contents are unspecified. */
 int kzgmi_open_quotient_device(kzgmi_ctx* ctx, kzgmi_curve curve, const void* d_coeffs, size_t m, const void* d_zs,
                                size_t k, void* d_ys_out, void* d_q_out);
+
+/* ---- power-of-two number-theoretic transforms over Fr -- both curves, batched.
+ * For a curve with scalar modulus r, w_n = g^((r-1)/n) with g = 7 on BLS12-381 (so w_8192 is the w of
+ * the EIP-7594 section) and g = 5 on BN254; both generate the whole 2-power subgroup (2-adicity 32 and
+ * 28).  n = 2^logn, 0 <= logn <= 26.  count >= 1 independent transforms of one size: transform t is at
+ * byte 32 n t of both arrays, count n <= 2^26; count == 0 succeeds and writes nothing.  Values are
+ * 32 B big-endian canonical Fr (a value >= r: KZGMI_ERR_SCALAR).  shift32 is a host pointer in every
+ * form (like seed32): NULL means s = 1, s >= r gives KZGMI_ERR_SCALAR, s = 0 KZGMI_ERR_ARG.
+ *   flags = 0 (forward):  out[j] = sum_{i<n} in[i] (s w_n^j)^i -- the polynomial with coefficients `in`
+ *                         evaluated on the coset s <w_n>
+ *   KZGMI_NTT_INVERSE:    the inverse map: from v[j] = p(s w_n^j) the n coefficients
+ *                         out[i] = s^-i n^-1 sum_j v[j] w_n^(-i j)
+ *   KZGMI_NTT_BITREV:     the evaluation side (a forward transform's output, an inverse one's input) is
+ *                         in bit-reversed order: index k holds the point s w_n^rev_logn(k), the blob and
+ *                         cell order of the EIP sections.  The coefficient side is always in natural order.
+ * Any other flag bit, logn > 26 or count n > 2^26: KZGMI_ERR_ARG.  logn = 0 is the identity after the
+ * range check.  The host form stages through slot 0 and copies the result back; the synchronous device
+ * form runs on slot 0; the async form runs on any slot and completes with kzgmi_slot_wait (ok_out = 1),
+ * which reports the device-side errors.  Device arrays are 16-byte aligned; d_out == d_in (in place) is
+ * allowed, any other overlap is KZGMI_ERR_ARG.  The range check belongs to the first pass over the data
+ * and there is no separate copy of the result: on an error the contents of `out` -- and of `in`, if the
+ * call was in place -- are unspecified (as kzgmi_recover_cells); the slot stays usable.  Scratch: per
+ * slot at most one more copy of the data (32 count n B; none up to 2^8 points), in the slot's workspace,
+ * grown on first use and counted by kzgmi_alloc_count, as are each curve's root tables (544 KiB, built
+ * at the curve's first transform) and the slot's shift table (512 KiB): a repeat call of the same shape
+ * allocates nothing.  (Read at context creation: KZGMI_NTT_PASS_BITS = 2 .. 8 bounds the bits of one
+ * pass over the data -- tests; KZGMI_NTT_TILE_BITS = 10 .. 12 selects a workgroup's tile of 2^10
+ * (shipped), 2^11 or 2^12 elements, with passes of at most that less two bits -- measurements.) */
+#define KZGMI_NTT_INVERSE 1u
+#define KZGMI_NTT_BITREV 2u
+int kzgmi_fr_ntt(kzgmi_ctx* ctx, kzgmi_curve curve, const uint8_t* in, unsigned logn, size_t count, uint32_t flags,
+                 const uint8_t* shift32, uint8_t* out);
+int kzgmi_fr_ntt_device(kzgmi_ctx* ctx, kzgmi_curve curve, const void* d_in, unsigned logn, size_t count, uint32_t flags,
+                        const uint8_t* shift32, void* d_out);
+int kzgmi_fr_ntt_device_async(kzgmi_ctx* ctx, kzgmi_curve curve, int slot, const void* d_in, unsigned logn, size_t count,
+                              uint32_t flags, const uint8_t* shift32, void* d_out);
+
+/* ---- KZG openings of a polynomial given by its evaluations: kzgmi_open on the polynomial whose
+ * n = 2^logn values on <w_n> of the key's curve are `evals` (n x 32 B, natural order, or bit-reversed
+ * with flags = KZGMI_NTT_BITREV -- no other flag; n <= the key's n).  One job: the inverse transform
+ * into a slot buffer, then the opening in coefficient form with m = n, with no host round trip.
+ * Outputs, the bound of k <= 4096 points, the conventions of the three forms and the scratch are those
+ * of kzgmi_open (plus the transform's); a point of the domain is no special case, its y is the given
+ * evaluation.  A value >= r in evals or zs: KZGMI_ERR_SCALAR; a call that fails writes no output. */
+int kzgmi_open_evals(kzgmi_ctx* ctx, const kzgmi_ck* ck, const uint8_t* evals, unsigned logn, uint32_t flags,
+                     const uint8_t* zs, size_t k, uint8_t* ys_out, uint8_t* proofs_out);
+int kzgmi_open_evals_device(kzgmi_ctx* ctx, const kzgmi_ck* ck, const void* d_evals, unsigned logn, uint32_t flags,
+                            const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out);
+int kzgmi_open_evals_device_async(kzgmi_ctx* ctx, const kzgmi_ck* ck, int slot, const void* d_evals, unsigned logn,
+                                  uint32_t flags, const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out);
 
 /* Optimal-ate pairing e(P, Q) for P in G1, Q in G2: 12 Fp values in tower order, big-endian:
  * 576 B (BLS12-381) / 384 B (BN254).  Test/diagnostic utility.  (ABI 2 returned e(P, Q)^3 on

@@ -253,6 +253,10 @@ int kzgmi_ctx_create_device(kzgmi_ctx** out, int device_id, int pipeline_slots) 
   if (const char* e = getenv("KZGMI_BLOB_HASH"))
     c->blob_hash = !strcmp(e, "lane") ? BlobLaunch::HASH_LANE : !strcmp(e, "wave") ? BlobLaunch::HASH_WAVE : 0;
   if (const char* e = getenv("KZGMI_OPEN_GROUP")) c->open_group = std::max<size_t>(1, strtoull(e, nullptr, 10));
+  if (const char* e = getenv("KZGMI_NTT_TILE_BITS"))
+    c->ntt_tile_bits = std::min<uint32_t>(std::max<uint32_t>(NTT_MIN_TILE_BITS, (uint32_t)atoi(e)), NTT_MAX_TILE_BITS);
+  if (const char* e = getenv("KZGMI_NTT_PASS_BITS"))
+    c->ntt_pass_bits = std::min<uint32_t>(std::max<uint32_t>(NTT_MIN_PASS_BITS, (uint32_t)atoi(e)), NTT_WIDEST_BITS);
   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless set before the runtime
   // starts) and serialises the streams of one queue, so every slot in flight needs a queue of its
   // own (16 slots on 24 queues pipeline; 24 on 24 ran 3.6x slower).  The runtime keeps that many
@@ -341,6 +345,7 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
   c->blob_table.release();
   c->cell_table.release();
   c->ntt_table.release();
+  for (DevBuf& b : c->fr_ntt_table) b.release();
   for (kzgmi_cell_srs* cs : c->cell_srs_list) {  // detach: later kzgmi_cell_srs_free() only deletes the structs
     cs->pts.release();
     cs->inf.release();

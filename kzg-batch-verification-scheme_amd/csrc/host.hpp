@@ -108,6 +108,7 @@ struct Slot {
   DevBuf bp_q, bp_part, bp_enc;                  // blob proofs (blobproof.hpp): quotients, partial sums and results, encodings
   DevBuf open_zp, open_q, open_aux;              // openings (open.hpp): the points' powers, a group's quotients, run and tile values
   DevBuf open_y, open_rec, open_enc;             // ... the evaluations, the proofs as records, their encodings
+  DevBuf ntt_tmp, ntt_call;                      // transforms (ntt.hpp): the ping-pong copy of the data, the call's shift table
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -139,7 +140,7 @@ struct Slot {
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
                       &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &cell_tab, &rec_z,
                       &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc,
-                      &open_zp, &open_q, &open_aux, &open_y, &open_rec, &open_enc,
+                      &open_zp, &open_q, &open_aux, &open_y, &open_rec, &open_enc, &ntt_tmp, &ntt_call,
                       &find_tab, &find_negt, &find_nodes, &find_flags, &find_rec, &find_ok};
     for (DevBuf* b : bufs) f(*b);
   }
@@ -221,6 +222,12 @@ struct kzgmi_ctx {
   // EIP-7594 cell extension and recovery (recover.hpp): twiddles and scale factors, built at the first such call
   DevBuf ntt_table;
   bool ntt_table_ready = false;
+  // Power-of-two transforms over Fr (ntt.hpp): each curve's root tables, built at its first transform.
+  // ntt_pass_bits: the most bits of a pass, KZGMI_NTT_PASS_BITS (tests: plans of many passes at small
+  // sizes); ntt_tile_bits: a workgroup's tile, KZGMI_NTT_TILE_BITS (A/B, tools/bench_ntt.py)
+  DevBuf fr_ntt_table[2];
+  bool fr_ntt_table_ready[2] = {false, false};
+  uint32_t ntt_pass_bits = NTT_WIDEST_BITS, ntt_tile_bits = NTT_TILE_BITS;  // (a pass has at most ntt_tile_bits - 2 bits)
   DevBuf gath;                       // multi-device: partial records gathered from every device
   DevBuf mdig, mdig_all;             // multi-device Fiat-Shamir: this device's / every device's subtree roots
   std::vector<kzgmi_ctx*> peers;     // multi-device: contexts of device_ids[1..] (kzgmi_ctx_create, n_devices > 1)
@@ -508,6 +515,22 @@ struct HostCore {
 };
 extern template struct HostCore<Bls12_381>;
 extern template struct HostCore<Bn254>;
+
+// ---- host_ntt.hip: the transforms over Fr, instantiated there for both curves
+template <class Cv>
+struct HostNtt {
+  // The passes of count transforms of 2^logn on s.stream, inside the caller's job (behind begin_job and
+  // the zeroed error word `err`): d_in -> d_out (the same array, or disjoint ones), either side big-endian
+  // bytes or 8 canonical little-endian words.  flags and the shift (nullptr: 1) are checked by the caller
+  // (ntt_check_args).  Grows the slot's scratch and builds the curve's tables at their first use.
+  static int enqueue(kzgmi_ctx* c, Slot& s, const void* d_in, unsigned logn, size_t count, uint32_t flags, const Seed* shift,
+                     bool read_be, bool write_be, void* d_out, uint32_t* err);
+};
+extern template struct HostNtt<Bls12_381>;
+extern template struct HostNtt<Bn254>;
+// logn, count, flags and shift32 of a transform call (shift_out / has_shift: s for HostNtt::enqueue)
+int ntt_check_args(int curve, unsigned logn, size_t count, uint32_t flags, const uint8_t* shift32, Seed* shift_out,
+                   bool* has_shift);
 
 // ---- host_batch.hip: the chunk digests of kzgmi_fs_chunk_digests_device, enqueued on slot 0's stream (no wait)
 int fs_chunk_digests_enqueue(kzgmi_ctx* c, kzgmi_curve curve, const void* dC, const void* dz, const void* dy,

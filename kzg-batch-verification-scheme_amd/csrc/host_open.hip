@@ -38,11 +38,21 @@ int check_open_args(const void* coeffs, size_t m, const void* zs, size_t k, cons
   return 0;
 }
 
-// The front end every form shares, on s.stream behind the zeroed error word: the coefficients as
-// canonical LE words in s.scal_s (range-checked once per call) and the powers of every point in
+// Where an opening's coefficients come from: m coefficients (32 B big-endian each), or with evals the
+// m = 2^logn values of the polynomial on the m-th roots of unity (ntt_flags: KZGMI_NTT_BITREV or 0)
+struct OpenSource {
+  const void* d;
+  bool evals;
+  unsigned logn;
+  uint32_t ntt_flags;
+};
+
+// The front end every form shares, which starts the job: on s.stream behind the zeroed error word, the
+// coefficients as canonical LE words in s.scal_s (range-checked once per call; from evaluations, the
+// inverse transform's passes, whose first range-checks them) and the powers of every point in
 // s.open_zp (each point range-checked)
 template <class Cv>
-int enqueue_open_inputs(Slot& s, const void* d_coeffs, size_t m, const void* d_zs, size_t k) {
+int enqueue_open_inputs(kzgmi_ctx* c, Slot& s, const OpenSource& src, size_t m, const void* d_zs, size_t k) {
   using L = Launch<Cv>;
   CHK(s.flags.ensure(16));
   CHK(s.scal_s.ensure(m * 32));
@@ -50,7 +60,10 @@ int enqueue_open_inputs(Slot& s, const void* d_coeffs, size_t m, const void* d_z
   CHK(begin_job(s));
   HIPCHK(hipMemsetAsync(s.flags.p, 0, 16, s.stream));
   uint32_t* err = s.flags.template as<uint32_t>() + 1;
-  L::convert_scalars(s.stream, (const uint8_t*)d_coeffs, (uint32_t)m, s.scal_s.template as<uint32_t>(), err);
+  if (src.evals)
+    CHK(HostNtt<Cv>::enqueue(c, s, src.d, src.logn, 1, KZGMI_NTT_INVERSE | src.ntt_flags, nullptr, true, false, s.scal_s.p, err));
+  else
+    L::convert_scalars(s.stream, (const uint8_t*)src.d, (uint32_t)m, s.scal_s.template as<uint32_t>(), err);
   L::open_points(s.stream, (const uint8_t*)d_zs, (uint32_t)k, s.open_zp.template as<uint32_t>(), err);
   return 0;
 }
@@ -59,7 +72,7 @@ int enqueue_open_inputs(Slot& s, const void* d_coeffs, size_t m, const void* d_z
 // kernels reporting through the slot's error word.  d_ys_out and d_proofs_out are written by the
 // emit kernels only, which write nothing once an error is raised.
 template <class Cv>
-int enqueue_open_job(kzgmi_ctx* c, Slot& s, const kzgmi_ck* ck, const void* d_coeffs, size_t m, const void* d_zs, size_t k,
+int enqueue_open_job(kzgmi_ctx* c, Slot& s, const kzgmi_ck* ck, const OpenSource& src, size_t m, const void* d_zs, size_t k,
                      void* d_ys_out, void* d_proofs_out) {
   using L = Launch<Cv>;
   using XY = Xyzz<Cv>;
@@ -72,7 +85,7 @@ int enqueue_open_job(kzgmi_ctx* c, Slot& s, const kzgmi_ck* ck, const void* d_co
   CHK(s.open_enc.ensure(k * gb));
   CHK(s.open_q.ensure(G * nq * 32));
   CHK(s.open_aux.ensure(open_aux_values(tiles, G) * 32));
-  CHK(enqueue_open_inputs<Cv>(s, d_coeffs, m, d_zs, k));
+  CHK(enqueue_open_inputs<Cv>(c, s, src, m, d_zs, k));
   hipStream_t st = s.stream;
   uint32_t* err = s.flags.template as<uint32_t>() + 1;
   XY* rec = s.open_rec.template as<XY>();
@@ -130,7 +143,8 @@ int kzgmi_open_device_async(kzgmi_ctx* c, const kzgmi_ck* ck, int slot, const vo
   CHK(check_open_args(d_coeffs, m, d_zs, k, d_ys_out, d_proofs_out, g1_bytes(ck->curve), true));
   Roctx rx("kzgmi_open_device_async");
   return dispatch(ck->curve, [&](auto cv) -> int {
-    return enqueue_open_job<decltype(cv)>(c, c->slots[slot], ck, d_coeffs, m, d_zs, k, d_ys_out, d_proofs_out);
+    return enqueue_open_job<decltype(cv)>(c, c->slots[slot], ck, OpenSource{d_coeffs, false, 0, 0}, m, d_zs, k, d_ys_out,
+                                          d_proofs_out);
   });
 }
 
@@ -156,7 +170,61 @@ int kzgmi_open(kzgmi_ctx* c, const kzgmi_ck* ck, const uint8_t* coeffs, size_t m
   uint8_t* d[4];
   CHK(stage_host(c, s, items, 4, d));
   CHK(dispatch(ck->curve, [&](auto cv) -> int {
-    return enqueue_open_job<decltype(cv)>(c, s, ck, d[0], m, d[1], k, d[3], d[2]);
+    return enqueue_open_job<decltype(cv)>(c, s, ck, OpenSource{d[0], false, 0, 0}, m, d[1], k, d[3], d[2]);
+  }));
+  CHK(finish_slot(c, s, nullptr));
+  HIPCHK(hipMemcpy(proofs_out, d[2], gb * k, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ys_out, d[3], 32 * k, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Openings of a polynomial given by its evaluations: the inverse transform into the slot's coefficient
+// buffer and the opening on those coefficients, one job
+int check_open_evals(const kzgmi_ctx* c, const kzgmi_ck* ck, unsigned logn, uint32_t flags) {
+  if (!ck || ck->ctx != c) return fail(KZGMI_ERR_ARG, "commit key does not belong to this context");
+  if (logn > NTT_MAX_LOGN) return fail(KZGMI_ERR_ARG, "transform too large (max 2^26 points)");
+  if (flags & ~(uint32_t)KZGMI_NTT_BITREV) return fail(KZGMI_ERR_ARG, "kzgmi_open_evals takes KZGMI_NTT_BITREV only");
+  if ((size_t(1) << logn) > ck->n) return fail(KZGMI_ERR_ARG, "more evaluations than commit-key points");
+  return 0;
+}
+
+int kzgmi_open_evals_device_async(kzgmi_ctx* c, const kzgmi_ck* ck, int slot, const void* d_evals, unsigned logn,
+                                  uint32_t flags, const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out) {
+  KZ_ROUTE(c, nullptr, slot);  // (commit keys live on the primary device: its slots only)
+  CHK(check_ctx(c, slot));
+  CHK(check_open_evals(c, ck, logn, flags));
+  const size_t m = size_t(1) << logn;
+  CHK(check_open_args(d_evals, m, d_zs, k, d_ys_out, d_proofs_out, g1_bytes(ck->curve), true));
+  Roctx rx("kzgmi_open_evals_device_async");
+  return dispatch(ck->curve, [&](auto cv) -> int {
+    return enqueue_open_job<decltype(cv)>(c, c->slots[slot], ck, OpenSource{d_evals, true, logn, flags}, m, d_zs, k, d_ys_out,
+                                          d_proofs_out);
+  });
+}
+
+int kzgmi_open_evals_device(kzgmi_ctx* c, const kzgmi_ck* ck, const void* d_evals, unsigned logn, uint32_t flags,
+                            const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out) {
+  CHK(check_ctx(c));
+  CHK(slot0_idle(c));
+  CHK(kzgmi_open_evals_device_async(c, ck, 0, d_evals, logn, flags, d_zs, k, d_ys_out, d_proofs_out));
+  return kzgmi_slot_wait(c, 0, nullptr);
+}
+
+// The host form: [evals | zs | proofs | ys] in slot 0's stage buffer, the results copied back
+int kzgmi_open_evals(kzgmi_ctx* c, const kzgmi_ck* ck, const uint8_t* evals, unsigned logn, uint32_t flags, const uint8_t* zs,
+                     size_t k, uint8_t* ys_out, uint8_t* proofs_out) {
+  CHK(check_ctx(c));
+  CHK(check_open_evals(c, ck, logn, flags));
+  const size_t m = size_t(1) << logn, gb = g1_bytes(ck->curve);
+  CHK(check_open_args(evals, m, zs, k, ys_out, proofs_out, gb, false));
+  CHK(slot0_idle(c));
+  if (k == 0) return 0;
+  Slot& s = c->slots[0];
+  const StageItem items[4] = {{evals, 32 * m}, {zs, 32 * k}, {nullptr, gb * k}, {nullptr, 32 * k}};
+  uint8_t* d[4];
+  CHK(stage_host(c, s, items, 4, d));
+  CHK(dispatch(ck->curve, [&](auto cv) -> int {
+    return enqueue_open_job<decltype(cv)>(c, s, ck, OpenSource{d[0], true, logn, flags}, m, d[1], k, d[3], d[2]);
   }));
   CHK(finish_slot(c, s, nullptr));
   HIPCHK(hipMemcpy(proofs_out, d[2], gb * k, hipMemcpyDeviceToHost));
@@ -181,7 +249,7 @@ int kzgmi_open_quotient_device(kzgmi_ctx* c, kzgmi_curve curve, const void* d_co
     Slot& s = c->slots[0];
     const size_t tiles = L::open_tiles(m), G = open_group_points(c, m, k), nq = m > 1 ? m - 1 : 0;
     CHK(s.open_aux.ensure(open_aux_values(tiles, G) * 32));
-    CHK(enqueue_open_inputs<Cv>(s, d_coeffs, m, d_zs, k));
+    CHK(enqueue_open_inputs<Cv>(c, s, OpenSource{d_coeffs, false, 0, 0}, m, d_zs, k));
     hipStream_t st = s.stream;
     if (m == 0) HIPCHK(hipMemsetAsync(d_ys_out, 0, k * 32, st));
     uint32_t* runv = s.open_aux.template as<uint32_t>();

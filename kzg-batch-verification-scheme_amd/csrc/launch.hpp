@@ -6,6 +6,7 @@
 #include "kernels.hpp"
 #include "msm_small.hpp"
 #include "find_plan.hpp"
+#include "ntt_plan.hpp"
 
 namespace kzgmi {
 
@@ -145,6 +146,17 @@ struct Launch {
   // tilev and tilec g x tiles
   static void open_quotients(hipStream_t st, const uint32_t* coef, uint32_t m, const uint32_t* zp, uint32_t g, uint32_t* runv,
                         uint32_t* tilev, uint32_t* tilec, uint8_t* ys, void* q, bool be);
+  // ---- power-of-two transforms over Fr (ntt.hpp, launch_ntt.hip)
+  static size_t ntt_table_bytes();  // the curve's root tables
+  static size_t ntt_call_bytes();   // a call's shift and scale table
+  static void ntt_roots(hipStream_t st, void* table);
+  // shift: s as a Seed (canonical, nonzero), or nullptr: s = 1 (then only the scale is written)
+  static void ntt_call_table(hipStream_t st, const Seed* shift, bool inverse, uint32_t logn, void* tab);
+  // one pass of a plan over count transforms of 2^logn, tiles of 2^tile_bits elements
+  // (NTT_MIN_TILE_BITS .. NTT_MAX_TILE_BITS, at least pass.bits + 2); a value >= r read by a
+  // NTT_P_READ_BE pass raises DERR_SCALAR
+  static void ntt_pass(hipStream_t st, uint32_t tile_bits, const NttPass& pass, uint32_t logn, uint64_t count, const void* in,
+                       void* out, const void* roots, const void* call, uint32_t* err);
   // ---- generators (launch_gen.hip)
   static void gen_table(hipStream_t st, XY* base, AF* table);
   static void gen_g1(hipStream_t st, const uint8_t* scalars, uint32_t n, const AF* table, uint8_t* out, uint32_t* err);

@@ -97,6 +97,12 @@ def lib():
         "kzgmi_open_device": ([vp, vp, vp, sz, vp, sz, vp, vp], c.c_int),
         "kzgmi_open_device_async": ([vp, vp, c.c_int, vp, sz, vp, sz, vp, vp], c.c_int),
         "kzgmi_open_quotient_device": ([vp, c.c_int, vp, sz, vp, sz, vp, vp], c.c_int),
+        "kzgmi_fr_ntt": ([vp, c.c_int, vp, c.c_uint, sz, c.c_uint32, u8p, vp], c.c_int),
+        "kzgmi_fr_ntt_device": ([vp, c.c_int, vp, c.c_uint, sz, c.c_uint32, u8p, vp], c.c_int),
+        "kzgmi_fr_ntt_device_async": ([vp, c.c_int, c.c_int, vp, c.c_uint, sz, c.c_uint32, u8p, vp], c.c_int),
+        "kzgmi_open_evals": ([vp, vp, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
+        "kzgmi_open_evals_device": ([vp, vp, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
+        "kzgmi_open_evals_device_async": ([vp, vp, c.c_int, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
         "kzgmi_fs_challenge_device": ([vp, c.c_int, vp, vp, vp, vp, sz, c.c_uint32, u8p], c.c_int),
         "kzgmi_fs_chunk_digests_device": ([vp, c.c_int, vp, vp, vp, vp, sz, c.c_uint64, c.c_uint32, vp], c.c_int),
         "kzgmi_fs_challenge_from_digests_device": ([vp, c.c_int, vp, sz, c.c_uint64, u8p], c.c_int),
@@ -242,6 +248,8 @@ def exported_symbols():
         "kzgmi_cell_coeffs_device", "kzgmi_cell_range_partials_device", "kzgmi_verify_cell_batch_find_invalid",
         "kzgmi_verify_cell_batch_find_invalid_device",
         "kzgmi_open", "kzgmi_open_device", "kzgmi_open_device_async", "kzgmi_open_quotient_device",
+        "kzgmi_fr_ntt", "kzgmi_fr_ntt_device", "kzgmi_fr_ntt_device_async",
+        "kzgmi_open_evals", "kzgmi_open_evals_device", "kzgmi_open_evals_device_async",
     ]
 
 
@@ -250,6 +258,9 @@ FLAG_SUBGROUP_CHECK = 2
 FLAG_POWERS = 4
 FLAG_FIAT_SHAMIR = 8
 FLAG_TRUSTED_G1 = 16
+NTT_INVERSE = 1  # KZGMI_NTT_INVERSE
+NTT_BITREV = 2   # KZGMI_NTT_BITREV: the evaluation side is in bit-reversed order
+NTT_MAX_LOGN = 26
 ERR_NOT_IN_SUBGROUP = -7
 FS_CHUNK = 4096
 BLOB_BYTES = 4096 * 32  # an EIP-4844 blob: 4096 big-endian canonical Fr elements
@@ -776,6 +787,111 @@ class Context:
         self._order(0)
         _check(lib().kzgmi_open_quotient_device(self.handle, CURVES[curve], *ptrs))
         return ys_out, out
+
+    # ------------------------------------------------------------------ transforms over Fr
+    @staticmethod
+    def _ntt_args(values, logn, count, inverse, bitrev, shift, nbytes):
+        if logn is None:
+            per = nbytes // 32 // max(1, count)
+            logn = max(per, 1).bit_length() - 1
+            if count < 1 or (32 << logn) * count != nbytes:
+                raise ValueError("values are not count transforms of 2^logn x 32 B: pass logn")
+        flags = (NTT_INVERSE if inverse else 0) | (NTT_BITREV if bitrev else 0)
+        if isinstance(shift, int):
+            if not 0 <= shift < (1 << 256):
+                raise ValueError("shift must be in [0, 2^256)")
+            shift = shift.to_bytes(32, "big")
+        elif shift is not None:
+            shift = bytes(shift)
+            if len(shift) != 32:
+                raise ValueError("shift must be 32 bytes, got %d" % len(shift))
+        return int(logn), flags, shift
+
+    def fr_ntt(self, curve: str, values, logn: Optional[int] = None, count: int = 1, inverse: bool = False,
+               bitrev: bool = False, shift=None, out=None):
+        """`count` transforms of n = 2^logn values of Fr (32 B big-endian canonical each, transform t at byte
+        32 n t): forward, out[j] = sum_i in[i] (s w_n^j)^i; inverse=True, the n coefficients from the values
+        on the coset s <w_n>; bitrev=True, the evaluation side in bit-reversed order.  shift: s as an int or
+        32 big-endian bytes (None: 1).  A device tensor in gives a device tensor out (`out` where given; the
+        input itself transforms in place); host bytes in give bytes out."""
+        if _is_device_tensor(values):
+            import torch
+            nbytes = values.numel() * values.element_size()
+            logn, flags, sh = self._ntt_args(values, logn, count, inverse, bitrev, shift, nbytes)
+            total = (32 << logn) * count
+            if out is None:
+                out = torch.empty(max(1, total), dtype=torch.uint8, device=values.device)[:total]
+            self._order(0)
+            _check(lib().kzgmi_fr_ntt_device(self.handle, CURVES[curve], _dptr(values, total) if count else None, logn,
+                                             int(count), flags, sh, _dptr(out, total) if count else None))
+            return out
+        hv = _host_ptr(values)
+        logn, flags, sh = self._ntt_args(values, logn, count, inverse, bitrev, shift, hv[1])
+        total = (32 << logn) * count
+        if hv[1] < total:
+            raise ValueError("input buffer shorter than count transforms of 2^logn values")
+        ob = ctypes.create_string_buffer(max(1, total))
+        _check(lib().kzgmi_fr_ntt(self.handle, CURVES[curve], hv[0] or None, logn, int(count), flags, sh,
+                                  ctypes.addressof(ob)))
+        del hv
+        return ob.raw[:total]
+
+    def fr_ntt_async(self, slot: int, curve: str, values, logn: int, count: int = 1, inverse: bool = False,
+                     bitrev: bool = False, shift=None, out=None):
+        """Enqueue fr_ntt() of device tensors on `slot` (out None: in place); wait(slot) completes it and
+        raises its device-side errors.  Returns the output tensor."""
+        logn, flags, sh = self._ntt_args(values, logn, count, inverse, bitrev, shift, 0)
+        total = (32 << logn) * count
+        if out is None:
+            out = values
+        self._order(slot)
+        _check(lib().kzgmi_fr_ntt_device_async(self.handle, CURVES[curve], int(slot), _dptr(values, total) if count else None,
+                                               logn, int(count), flags, sh, _dptr(out, total) if count else None))
+        return out
+
+    def open_evals(self, ck: CommitKey, evals, zs, logn: Optional[int] = None, k: Optional[int] = None,
+                   bitrev: bool = False, ys_out=None, out=None):
+        """open() of the polynomial given by its n = 2^logn <= ck.n values on the n-th roots of unity (32 B
+        each; bitrev=True: in bit-reversed order): (proofs, ys) as open() returns them.  The inverse
+        transform and the opening run as one job on the device."""
+        gb = 2 * FP_BYTES[ck.curve]
+        flags = NTT_BITREV if bitrev else 0
+        if _is_device_tensor(zs):
+            import torch
+            if logn is None:
+                logn = max(evals.numel() * evals.element_size() // 32, 1).bit_length() - 1
+            if k is None:
+                k = zs.numel() * zs.element_size() // 32
+            if out is None:
+                out = torch.empty(max(1, k) * gb, dtype=torch.uint8, device=zs.device)[:k * gb]
+            if ys_out is None:
+                ys_out = torch.empty(max(1, k) * 32, dtype=torch.uint8, device=zs.device)[:k * 32]
+            ptrs = (_dptr(evals, 32 << logn), int(logn), flags, _dptr(zs, 32 * k), int(k), _dptr(ys_out, 32 * k),
+                    _dptr(out, gb * k))
+            self._order(0)
+            _check(lib().kzgmi_open_evals_device(self.handle, ck.handle, *ptrs))
+            return out, ys_out
+        he, hz = _host_ptr(evals), _host_ptr(zs)
+        if logn is None:
+            logn = max(he[1] // 32, 1).bit_length() - 1
+        if k is None:
+            k = hz[1] // 32
+        if he[1] < (32 << logn) or hz[1] < 32 * k:
+            raise ValueError("input buffers shorter than 2^logn evaluations / k points")
+        pb, yb = ctypes.create_string_buffer(max(1, k * gb)), ctypes.create_string_buffer(max(1, k * 32))
+        _check(lib().kzgmi_open_evals(self.handle, ck.handle, he[0] or None, int(logn), flags, hz[0] or None, int(k),
+                                      ctypes.addressof(yb), ctypes.addressof(pb)))
+        del he, hz
+        return pb.raw[:k * gb], yb.raw[:k * 32]
+
+    def open_evals_async(self, ck: CommitKey, slot: int, evals, zs, logn: int, k: int, ys_out, out, bitrev: bool = False):
+        """Enqueue open_evals() of device tensors on `slot`; wait(slot) completes it (and raises its
+        device-side errors)."""
+        gb = 2 * FP_BYTES[ck.curve]
+        ptrs = (_dptr(evals, 32 << logn), int(logn), NTT_BITREV if bitrev else 0, _dptr(zs, 32 * k), int(k),
+                _dptr(ys_out, 32 * k), _dptr(out, gb * k))
+        self._order(slot)
+        _check(lib().kzgmi_open_evals_device_async(self.handle, ck.handle, int(slot), *ptrs))
 
     # ------------------------------------------------------------------ Fiat-Shamir
     def commit_async(self, ck: CommitKey, slot: int, coeffs, m: int):
@@ -1716,6 +1832,17 @@ def compute_cells_and_proofs(pk: CellProofKey, blobs, n: Optional[int] = None, c
 def recover_cells_and_proofs(pk: CellProofKey, cell_indices, cells, n_blobs: Optional[int] = None):
     """Context.recover_cells_and_proofs on the key's context."""
     return pk.ctx.recover_cells_and_proofs(pk, cell_indices, cells, n_blobs)
+
+
+def fr_ntt(curve: str, values, logn: Optional[int] = None, count: int = 1, inverse: bool = False, bitrev: bool = False,
+           shift=None, out=None, ctx: Optional[Context] = None):
+    """Power-of-two transforms over Fr on the GPU (Context.fr_ntt)."""
+    return (ctx or default_context()).fr_ntt(curve, values, logn, count, inverse, bitrev, shift, out)
+
+
+def open_evals(ck: CommitKey, evals, zs, logn: Optional[int] = None, k: Optional[int] = None, bitrev: bool = False):
+    """Context.open_evals on the key's context."""
+    return ck.ctx.open_evals(ck, evals, zs, logn, k, bitrev)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:
