@@ -73,7 +73,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * kzgmi_verify_blob_batch_find_invalid*, kzgmi_find_invalid_stats, and the cell search entry points
  * kzgmi_cell_coeffs_device, kzgmi_cell_range_partials_device, kzgmi_verify_cell_batch_find_invalid*,
  * and the opening entry points kzgmi_open*, kzgmi_open_quotient_device, and the transform entry points
- * kzgmi_fr_ntt* with the evaluation-form openings kzgmi_open_evals*.
+ * kzgmi_fr_ntt* with the evaluation-form openings kzgmi_open_evals*, and the transforms over G1
+ * kzgmi_g1_ntt* with the openings at every point of a domain, kzgmi_open_all_key_* and kzgmi_open_all*.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -763,6 +764,68 @@ int kzgmi_open_evals_device(kzgmi_ctx* ctx, const kzgmi_ck* ck, const void* d_ev
                             const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out);
 int kzgmi_open_evals_device_async(kzgmi_ctx* ctx, const kzgmi_ck* ck, int slot, const void* d_evals, unsigned logn,
                                   uint32_t flags, const void* d_zs, size_t k, void* d_ys_out, void* d_proofs_out);
+
+/* ---- power-of-two transforms over G1 -- both curves, batched.  n = 2^logn and w_n exactly
+ * as in the kzgmi_fr_ntt section; [k] P is the scalar multiple.  count independent transforms of one size,
+ * transform t at byte (96 | 64) n t of both arrays.
+ *   flags = 0 (forward):  out[j] = sum_{i<n} [w_n^(i j)] in[i]
+ *   KZGMI_NTT_INVERSE:    out[i] = [n^-1] sum_{j<n} [w_n^(-i j)] in[j]
+ *   KZGMI_NTT_BITREV:     the evaluation side (a forward transform's output, an inverse one's input) is in
+ *                         bit-reversed order, with the same meaning as for kzgmi_fr_ntt
+ * 0 <= logn <= 20 and count n <= 2^20; count == 0 succeeds and writes nothing.  Any other flag bit or a
+ * bound passed: KZGMI_ERR_ARG.  Points are uncompressed encodings of the curve (96 B / 64 B) in and out,
+ * infinity as everywhere in this header.  Inputs are validated as kzgmi_g1_fft128_device validates them:
+ * KZGMI_ERR_ENCODING for a bad encoding, KZGMI_ERR_NOT_ON_CURVE for a point off the curve.  There is no
+ * subgroup check, and the roots of unity act as integers below r: for on-curve inputs outside G1 the
+ * result is unspecified (as the GLV split under KZGMI_FLAG_TRUSTED_G1).  The three forms follow the
+ * header's conventions: the host form stages through slot 0; the synchronous device form runs on slot 0;
+ * the async form runs on any slot and completes with kzgmi_slot_wait (ok_out = 1), which reports the
+ * device-side errors.  Device arrays are 16-byte aligned; d_out == d_in (in place) is allowed, any other
+ * overlap is KZGMI_ERR_ARG.  The output is written by one last kernel that writes nothing once an error
+ * is raised: a failing call leaves `out` untouched and the slot usable.  Scratch, in the slot's workspace,
+ * grown on first use and counted by kzgmi_alloc_count (a repeat call of the same shape allocates nothing):
+ * the decoded points, two vectors of count n XYZZ records (192 B / 128 B each) and the encodings; and each
+ * curve's root tables of the kzgmi_fr_ntt section.  On BLS12-381 at logn = 7 the result equals
+ * kzgmi_g1_fft128_device's.  (Read at context creation: KZGMI_G1NTT_FORM = thread | wave forces one form of
+ * the radix-2 stages -- a thread or a wave per butterfly; unset, a call whose stages have at most 2^14
+ * butterflies takes the wave form.  The results are identical -- tests, measurements.) */
+int kzgmi_g1_ntt(kzgmi_ctx* ctx, kzgmi_curve curve, const uint8_t* in, unsigned logn, size_t count, uint32_t flags,
+                 uint8_t* out);
+int kzgmi_g1_ntt_device(kzgmi_ctx* ctx, kzgmi_curve curve, const void* d_in, unsigned logn, size_t count, uint32_t flags,
+                        void* d_out);
+int kzgmi_g1_ntt_device_async(kzgmi_ctx* ctx, kzgmi_curve curve, int slot, const void* d_in, unsigned logn, size_t count,
+                              uint32_t flags, void* d_out);
+
+/* ---- KZG openings at every point of a domain (FK20).  For p = sum_{i<m} c_i X^i with
+ * m <= n = 2^logn (read as zero above m) and every e < n:
+ *   ys[e] = p(w_n^e),   proofs[e] = [((p - ys[e]) / (X - w_n^e))(tau)]_1
+ * -- entry e is exactly what kzgmi_open returns for z = w_n^e, byte for byte: n uncompressed G1 encodings
+ * and n x 32 B big-endian evaluations.  flags = KZGMI_NTT_BITREV puts entry e at index rev_logn(e) of both
+ * outputs; no other flag is accepted.  ys_out may be NULL (proofs only).  At logn = 0 the proof is the
+ * point at infinity and y = c_0.
+ * The key (kzgmi_open_all_key_load) belongs to one commit key's curve and one logn, 0 <= logn <= 19, and
+ * needs n - 1 <= the commit key's n.  It is derived on the device from the commit key's resident row of
+ * powers (no second upload of the SRS), lives on the context's primary device like the other keys and
+ * holds 2n XYZZ records (192 MiB on BLS12-381 at logn = 19: kzgmi_open_all_key_device_bytes); the commit
+ * key may be freed afterwards.  Loading runs on slot 0, which must be idle.  An SRS with tau in the
+ * domain makes entries of the key infinite; the results are still kzgmi_open's.
+ * Errors: KZGMI_ERR_SCALAR for a coefficient >= r; KZGMI_ERR_ARG for m > n, a key of another context,
+ * logn out of range, a key needing more powers than the commit key has, a stray flag, misaligned or
+ * overlapping device arrays.  The three forms, the alignment rule and the completion of the async form are
+ * those of kzgmi_open; outputs overlap neither the input nor each other; a failing call writes no output
+ * and leaves the slot usable.  Scratch in the slot's workspace as for kzgmi_g1_ntt with 2n records, plus
+ * 5n scalars (the coefficients, their 2n-point transform, a padded copy, the evaluations) and the
+ * kzgmi_fr_ntt scratch of a 2n-point transform. */
+typedef struct kzgmi_open_all_key kzgmi_open_all_key;
+int kzgmi_open_all_key_load(kzgmi_ctx* ctx, const kzgmi_ck* ck, unsigned logn, kzgmi_open_all_key** out);
+void kzgmi_open_all_key_free(kzgmi_open_all_key* key);
+size_t kzgmi_open_all_key_device_bytes(const kzgmi_open_all_key* key);
+int kzgmi_open_all(kzgmi_ctx* ctx, const kzgmi_open_all_key* key, const uint8_t* coeffs, size_t m, uint32_t flags,
+                   uint8_t* ys_out, uint8_t* proofs_out);
+int kzgmi_open_all_device(kzgmi_ctx* ctx, const kzgmi_open_all_key* key, const void* d_coeffs, size_t m, uint32_t flags,
+                          void* d_ys_out, void* d_proofs_out);
+int kzgmi_open_all_device_async(kzgmi_ctx* ctx, const kzgmi_open_all_key* key, int slot, const void* d_coeffs, size_t m,
+                                uint32_t flags, void* d_ys_out, void* d_proofs_out);
 
 /* Optimal-ate pairing e(P, Q) for P in G1, Q in G2: 12 Fp values in tower order, big-endian:
  * 576 B (BLS12-381) / 384 B (BN254).  Test/diagnostic utility.  (ABI 2 returned e(P, Q)^3 on

@@ -255,6 +255,8 @@ int kzgmi_ctx_create_device(kzgmi_ctx** out, int device_id, int pipeline_slots) 
   if (const char* e = getenv("KZGMI_OPEN_GROUP")) c->open_group = std::max<size_t>(1, strtoull(e, nullptr, 10));
   if (const char* e = getenv("KZGMI_NTT_TILE_BITS"))
     c->ntt_tile_bits = std::min<uint32_t>(std::max<uint32_t>(NTT_MIN_TILE_BITS, (uint32_t)atoi(e)), NTT_MAX_TILE_BITS);
+  if (const char* e = getenv("KZGMI_G1NTT_FORM"))
+    c->g1ntt_form = !strcmp(e, "thread") ? G1NTT_FORM_THREAD : !strcmp(e, "wave") ? G1NTT_FORM_WAVE : G1NTT_FORM_AUTO;
   if (const char* e = getenv("KZGMI_NTT_PASS_BITS"))
     c->ntt_pass_bits = std::min<uint32_t>(std::max<uint32_t>(NTT_MIN_PASS_BITS, (uint32_t)atoi(e)), NTT_WIDEST_BITS);
   // HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless set before the runtime
@@ -361,6 +363,7 @@ void kzgmi_ctx_destroy(kzgmi_ctx* c) {
     pk->tab_inf.release();
     pk->ctx = nullptr;
   }
+  open_all_keys_detach(c);
   for (kzgmi_ck* ck : c->ck_list) {  // detach: later kzgmi_ck_free() only deletes the struct
     ck->pts.release();
     ck->inf.release();

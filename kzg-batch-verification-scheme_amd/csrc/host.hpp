@@ -109,6 +109,8 @@ struct Slot {
   DevBuf open_zp, open_q, open_aux;              // openings (open.hpp): the points' powers, a group's quotients, run and tile values
   DevBuf open_y, open_rec, open_enc;             // ... the evaluations, the proofs as records, their encodings
   DevBuf ntt_tmp, ntt_call;                      // transforms (ntt.hpp): the ping-pong copy of the data, the call's shift table
+  DevBuf g1_a, g1_b, g1_enc;                     // transforms over G1 (g1ntt.hpp): two record vectors, the encodings
+  DevBuf oa_scal;                                // open_all: ahat (2n scalars) and the coefficients padded to n
   DevBuf glv_r, glv_s, glv_t;                    // GLV half scalars (glv.hpp): [h0 x n | h1 x n]
   DevBuf digits;                                 // signed window digit codes of every term (msm.hpp)
   DevBuf small_nodes, small_flags;               // small calls' summation tree (msm_small.hpp)
@@ -140,7 +142,7 @@ struct Slot {
                       &fs_tmp, &fs_top, &pow, &chal, &glv_r, &glv_s, &glv_t, &digits, &small_nodes, &small_flags,
                       &acc29b, &cntb, &offb, &blob_z, &blob_y, &cell_part, &cell_coef, &cell_tab, &rec_z,
                       &fk_coef, &fk_scal, &fk_a, &fk_b, &fk_enc, &bp_q, &bp_part, &bp_enc,
-                      &open_zp, &open_q, &open_aux, &open_y, &open_rec, &open_enc, &ntt_tmp, &ntt_call,
+                      &open_zp, &open_q, &open_aux, &open_y, &open_rec, &open_enc, &ntt_tmp, &ntt_call, &g1_a, &g1_b, &g1_enc, &oa_scal,
                       &find_tab, &find_negt, &find_nodes, &find_flags, &find_rec, &find_ok};
     for (DevBuf* b : bufs) f(*b);
   }
@@ -152,6 +154,7 @@ using namespace kzgmi;
 struct kzgmi_cell_srs;
 struct kzgmi_cell_pk;
 struct kzgmi_blob_pk;
+struct kzgmi_open_all_key;
 
 struct kzgmi_ctx {
   int device = 0;
@@ -228,6 +231,8 @@ struct kzgmi_ctx {
   DevBuf fr_ntt_table[2];
   bool fr_ntt_table_ready[2] = {false, false};
   uint32_t ntt_pass_bits = NTT_WIDEST_BITS, ntt_tile_bits = NTT_TILE_BITS;  // (a pass has at most ntt_tile_bits - 2 bits)
+  // Transforms over G1 (g1ntt.hpp): the stage form, KZGMI_G1NTT_FORM=thread|wave forces one (tests, measurements)
+  int g1ntt_form = G1NTT_FORM_AUTO;
   DevBuf gath;                       // multi-device: partial records gathered from every device
   DevBuf mdig, mdig_all;             // multi-device Fiat-Shamir: this device's / every device's subtree roots
   std::vector<kzgmi_ctx*> peers;     // multi-device: contexts of device_ids[1..] (kzgmi_ctx_create, n_devices > 1)
@@ -236,6 +241,7 @@ struct kzgmi_ctx {
   std::vector<kzgmi_cell_srs*> cell_srs_list;  // live cell SRS objects: same (their inner kzgmi_srs is in srs_list)
   std::vector<kzgmi_cell_pk*> cell_pk_list;    // live cell proof keys: same
   std::vector<kzgmi_blob_pk*> blob_pk_list;    // live blob proof keys: same
+  std::vector<kzgmi_open_all_key*> open_all_key_list;  // live open_all keys (host_g1ntt.hip): same, through open_all_keys_detach
 };
 
 // prover commit key: rows w = 0..15 of 2^(16 w)-shifted SRS points, [row][point] Montgomery affine
@@ -531,6 +537,10 @@ extern template struct HostNtt<Bn254>;
 // logn, count, flags and shift32 of a transform call (shift_out / has_shift: s for HostNtt::enqueue)
 int ntt_check_args(int curve, unsigned logn, size_t count, uint32_t flags, const uint8_t* shift32, Seed* shift_out,
                    bool* has_shift);
+
+// ---- host_g1ntt.hip: kzgmi_ctx_destroy's detach of the context's live open_all keys (device memory freed; a
+// later kzgmi_open_all_key_free only deletes the struct)
+void open_all_keys_detach(kzgmi_ctx* c);
 
 // ---- host_batch.hip: the chunk digests of kzgmi_fs_chunk_digests_device, enqueued on slot 0's stream (no wait)
 int fs_chunk_digests_enqueue(kzgmi_ctx* c, kzgmi_curve curve, const void* dC, const void* dz, const void* dy,

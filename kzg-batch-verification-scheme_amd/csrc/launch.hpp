@@ -10,6 +10,11 @@
 
 namespace kzgmi {
 
+constexpr int G1NTT_FORM_AUTO = 0, G1NTT_FORM_THREAD = 1, G1NTT_FORM_WAVE = 2;  // the stage forms of g1ntt.hpp
+constexpr unsigned G1NTT_MAX_LOGN = 20;     // kzgmi_g1_ntt: count * n <= 2^20 points per call
+constexpr unsigned OPEN_ALL_MAX_LOGN = 19;  // kzgmi_open_all: its 2n-point transforms stay within that
+static_assert(OPEN_ALL_MAX_LOGN + 1 <= G1NTT_MAX_LOGN, "open_all's 2n-point transform is a transform the library runs");
+
 template <class Cv>
 struct Launch {
   using XY = Xyzz<Cv>;
@@ -157,6 +162,24 @@ struct Launch {
   // NTT_P_READ_BE pass raises DERR_SCALAR
   static void ntt_pass(hipStream_t st, uint32_t tile_bits, const NttPass& pass, uint32_t logn, uint64_t count, const void* in,
                        void* out, const void* roots, const void* call, uint32_t* err);
+  // ---- power-of-two transforms over G1 and kzgmi_open_all (g1ntt.hpp, launch_g1ntt.hip)
+  // validated points -> records; rev: every transform of 2^logn gathered through the bit reversal
+  static void g1ntt_from_affine(hipStream_t st, const AF* pts, const uint8_t* inf, uint32_t total, uint32_t logn, bool rev,
+                                XY* out);
+  // the logn stages of count transforms in place: natural order in, bit-reversed order out, the
+  // inverse not scaled by 1 / n.  roots: the curve's table of ntt_roots.  form: G1NTT_FORM_AUTO takes a wave per
+  // butterfly where a stage has few of them and a thread per butterfly above (g1ntt.hpp), the others force one
+  static void g1ntt_stages(hipStream_t st, XY* data, uint32_t logn, uint32_t count, bool inverse, const void* roots,
+                           int form);
+  // out[i] = [scal[i]] in[i] (8 canonical LE words each), or [2^-logn] in[i] with scal == nullptr; in == out allowed
+  static void g1ntt_mul(hipStream_t st, const XY* in, const uint32_t* scal, uint32_t logn, uint32_t total, XY* out);
+  static void g1ntt_rev(hipStream_t st, const XY* in, uint32_t logn, uint32_t total, XY* out);  // in != out
+  // kzgmi_open_all: the key's vector x (2n records) from a commit key's resident row of powers; the shift
+  // (h_0 .. h_{n-2}, infinity) out of the inverse 2n-point transform's output; a = (c_0 .. c_{m-1}, 0 ..) / 2^halvings
+  // of 2^lg scalars (8 LE words each)
+  static void g1ntt_key_x(hipStream_t st, const AF* srs29, const uint8_t* srs_inf, uint32_t logn, XY* x);
+  static void g1ntt_shift(hipStream_t st, const XY* ihat, uint32_t logn, XY* d);
+  static void g1ntt_pad(hipStream_t st, const uint32_t* coef, uint32_t m, uint32_t lg, uint32_t halvings, uint32_t* a);
   // ---- generators (launch_gen.hip)
   static void gen_table(hipStream_t st, XY* base, AF* table);
   static void gen_g1(hipStream_t st, const uint8_t* scalars, uint32_t n, const AF* table, uint8_t* out, uint32_t* err);

@@ -100,6 +100,15 @@ def lib():
         "kzgmi_fr_ntt": ([vp, c.c_int, vp, c.c_uint, sz, c.c_uint32, u8p, vp], c.c_int),
         "kzgmi_fr_ntt_device": ([vp, c.c_int, vp, c.c_uint, sz, c.c_uint32, u8p, vp], c.c_int),
         "kzgmi_fr_ntt_device_async": ([vp, c.c_int, c.c_int, vp, c.c_uint, sz, c.c_uint32, u8p, vp], c.c_int),
+        "kzgmi_g1_ntt": ([vp, c.c_int, vp, c.c_uint, sz, c.c_uint32, vp], c.c_int),
+        "kzgmi_g1_ntt_device": ([vp, c.c_int, vp, c.c_uint, sz, c.c_uint32, vp], c.c_int),
+        "kzgmi_g1_ntt_device_async": ([vp, c.c_int, c.c_int, vp, c.c_uint, sz, c.c_uint32, vp], c.c_int),
+        "kzgmi_open_all_key_load": ([vp, vp, c.c_uint, c.POINTER(vp)], c.c_int),
+        "kzgmi_open_all_key_free": ([vp], None),
+        "kzgmi_open_all_key_device_bytes": ([vp], sz),
+        "kzgmi_open_all": ([vp, vp, vp, sz, c.c_uint32, vp, vp], c.c_int),
+        "kzgmi_open_all_device": ([vp, vp, vp, sz, c.c_uint32, vp, vp], c.c_int),
+        "kzgmi_open_all_device_async": ([vp, vp, c.c_int, vp, sz, c.c_uint32, vp, vp], c.c_int),
         "kzgmi_open_evals": ([vp, vp, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
         "kzgmi_open_evals_device": ([vp, vp, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
         "kzgmi_open_evals_device_async": ([vp, vp, c.c_int, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
@@ -250,6 +259,9 @@ def exported_symbols():
         "kzgmi_open", "kzgmi_open_device", "kzgmi_open_device_async", "kzgmi_open_quotient_device",
         "kzgmi_fr_ntt", "kzgmi_fr_ntt_device", "kzgmi_fr_ntt_device_async",
         "kzgmi_open_evals", "kzgmi_open_evals_device", "kzgmi_open_evals_device_async",
+        "kzgmi_g1_ntt", "kzgmi_g1_ntt_device", "kzgmi_g1_ntt_device_async",
+        "kzgmi_open_all_key_load", "kzgmi_open_all_key_free", "kzgmi_open_all_key_device_bytes",
+        "kzgmi_open_all", "kzgmi_open_all_device", "kzgmi_open_all_device_async",
     ]
 
 
@@ -506,6 +518,26 @@ class CommitKey:
         try:
             if self.handle:
                 lib().kzgmi_ck_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class OpenAllKey:
+    """Key of open_all for one commit key and one domain size 2^logn: the transform of the SRS."""
+    ctx: "Context"
+    curve: str
+    logn: int
+    handle: ctypes.c_void_p
+
+    @property
+    def device_bytes(self) -> int:
+        return int(lib().kzgmi_open_all_key_device_bytes(self.handle))
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().kzgmi_open_all_key_free(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -892,6 +924,103 @@ class Context:
                 _dptr(ys_out, 32 * k), _dptr(out, gb * k))
         self._order(slot)
         _check(lib().kzgmi_open_evals_device_async(self.handle, ck.handle, int(slot), *ptrs))
+
+    # ------------------------------------------------------------------ transforms over G1, openings on a whole domain
+    def g1_ntt(self, curve: str, points, logn: Optional[int] = None, count: int = 1, inverse: bool = False,
+               bitrev: bool = False, out=None):
+        """`count` transforms of n = 2^logn points of G1 (uncompressed encodings, transform t at byte
+        96 | 64 times n t): forward, out[j] = sum_i [w_n^(i j)] in[i]; inverse=True, the inverse map;
+        bitrev=True, the evaluation side in bit-reversed order.  A device tensor in gives a device tensor
+        out (`out` where given; the input itself transforms in place); host bytes in give bytes out."""
+        gb = 2 * FP_BYTES[curve]
+        flags = (NTT_INVERSE if inverse else 0) | (NTT_BITREV if bitrev else 0)
+        dev = _is_device_tensor(points)
+        hv = None if dev else _host_ptr(points)
+        nbytes = points.numel() * points.element_size() if dev else hv[1]
+        if logn is None:
+            per = nbytes // gb // max(1, count)
+            logn = max(per, 1).bit_length() - 1
+            if count < 1 or (gb << logn) * count != nbytes:
+                raise ValueError("points are not count transforms of 2^logn encodings: pass logn")
+        logn = int(logn)
+        total = (gb << logn) * count
+        if dev:
+            import torch
+            if out is None:
+                out = torch.empty(max(1, total), dtype=torch.uint8, device=points.device)[:total]
+            self._order(0)
+            _check(lib().kzgmi_g1_ntt_device(self.handle, CURVES[curve], _dptr(points, total) if count else None, logn,
+                                             int(count), flags, _dptr(out, total) if count else None))
+            return out
+        if hv[1] < total:
+            raise ValueError("input buffer shorter than count transforms of 2^logn points")
+        ob = ctypes.create_string_buffer(max(1, total))
+        _check(lib().kzgmi_g1_ntt(self.handle, CURVES[curve], hv[0] or None, logn, int(count), flags, ctypes.addressof(ob)))
+        del hv
+        return ob.raw[:total]
+
+    def g1_ntt_async(self, slot: int, curve: str, points, logn: int, count: int = 1, inverse: bool = False,
+                     bitrev: bool = False, out=None):
+        """Enqueue g1_ntt() of device tensors on `slot` (out None: in place); wait(slot) completes it and
+        raises its device-side errors.  Returns the output tensor."""
+        flags = (NTT_INVERSE if inverse else 0) | (NTT_BITREV if bitrev else 0)
+        total = ((2 * FP_BYTES[curve]) << int(logn)) * count
+        if out is None:
+            out = points
+        self._order(slot)
+        _check(lib().kzgmi_g1_ntt_device_async(self.handle, CURVES[curve], int(slot), _dptr(points, total) if count else None,
+                                               int(logn), int(count), flags, _dptr(out, total) if count else None))
+        return out
+
+    def load_open_all_key(self, ck: CommitKey, logn: int) -> OpenAllKey:
+        """The key of open_all on the 2^logn-th roots of unity, derived on the device from `ck`."""
+        h = ctypes.c_void_p()
+        self._order(0)
+        _check(lib().kzgmi_open_all_key_load(self.handle, ck.handle, int(logn), ctypes.byref(h)))
+        key = OpenAllKey()
+        key.ctx, key.curve, key.logn, key.handle = self, ck.curve, int(logn), h
+        return key
+
+    def open_all(self, key: OpenAllKey, coeffs, m: Optional[int] = None, bitrev: bool = False, want_ys: bool = True,
+                 ys_out=None, out=None):
+        """KZG openings of p = sum_i coeff_i X^i (m <= n = 2^key.logn coefficients, 32 B each) at all n
+        points w_n^e: (proofs, ys) -- entry e is open()'s result for z = w_n^e (bitrev=True: at index
+        rev(e)); ys is None with want_ys=False.  Device tensors in: device tensors out; host bytes in:
+        bytes out."""
+        gb, n = 2 * FP_BYTES[key.curve], 1 << key.logn
+        flags = NTT_BITREV if bitrev else 0
+        if _is_device_tensor(coeffs):
+            import torch
+            if m is None:
+                m = coeffs.numel() * coeffs.element_size() // 32
+            if out is None:
+                out = torch.empty(n * gb, dtype=torch.uint8, device=coeffs.device)
+            if ys_out is None and want_ys:
+                ys_out = torch.empty(n * 32, dtype=torch.uint8, device=coeffs.device)
+            self._order(0)
+            _check(lib().kzgmi_open_all_device(self.handle, key.handle, _dptr(coeffs, 32 * m) if m else None, int(m), flags,
+                                               _dptr(ys_out, 32 * n) if ys_out is not None else None, _dptr(out, gb * n)))
+            return out, ys_out
+        hc = _host_ptr(coeffs)
+        if m is None:
+            m = hc[1] // 32
+        if hc[1] < 32 * m:
+            raise ValueError("input buffer shorter than m coefficients")
+        pb = ctypes.create_string_buffer(n * gb)
+        yb = ctypes.create_string_buffer(n * 32) if want_ys else None
+        _check(lib().kzgmi_open_all(self.handle, key.handle, hc[0] or None, int(m), flags,
+                                    ctypes.addressof(yb) if want_ys else None, ctypes.addressof(pb)))
+        del hc
+        return pb.raw, (yb.raw if want_ys else None)
+
+    def open_all_async(self, key: OpenAllKey, slot: int, coeffs, m: int, ys_out, out, bitrev: bool = False):
+        """Enqueue open_all() of device tensors on `slot` (ys_out may be None); wait(slot) completes it
+        (and raises its device-side errors)."""
+        gb, n = 2 * FP_BYTES[key.curve], 1 << key.logn
+        self._order(slot)
+        _check(lib().kzgmi_open_all_device_async(self.handle, key.handle, int(slot), _dptr(coeffs, 32 * m) if m else None,
+                                                 int(m), NTT_BITREV if bitrev else 0,
+                                                 _dptr(ys_out, 32 * n) if ys_out is not None else None, _dptr(out, gb * n)))
 
     # ------------------------------------------------------------------ Fiat-Shamir
     def commit_async(self, ck: CommitKey, slot: int, coeffs, m: int):
@@ -1843,6 +1972,17 @@ def fr_ntt(curve: str, values, logn: Optional[int] = None, count: int = 1, inver
 def open_evals(ck: CommitKey, evals, zs, logn: Optional[int] = None, k: Optional[int] = None, bitrev: bool = False):
     """Context.open_evals on the key's context."""
     return ck.ctx.open_evals(ck, evals, zs, logn, k, bitrev)
+
+
+def g1_ntt(curve: str, points, logn: Optional[int] = None, count: int = 1, inverse: bool = False, bitrev: bool = False,
+           out=None, ctx: Optional[Context] = None):
+    """Power-of-two transforms over G1 on the GPU (Context.g1_ntt)."""
+    return (ctx or default_context()).g1_ntt(curve, points, logn, count, inverse, bitrev, out)
+
+
+def open_all(key: OpenAllKey, coeffs, m: Optional[int] = None, bitrev: bool = False, want_ys: bool = True):
+    """Context.open_all on the key's context."""
+    return key.ctx.open_all(key, coeffs, m, bitrev, want_ys)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:
