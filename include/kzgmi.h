@@ -74,7 +74,8 @@ typedef enum { KZGMI_BLS12_381 = 0, KZGMI_BN254 = 1 } kzgmi_curve;
  * kzgmi_cell_coeffs_device, kzgmi_cell_range_partials_device, kzgmi_verify_cell_batch_find_invalid*,
  * and the opening entry points kzgmi_open*, kzgmi_open_quotient_device, and the transform entry points
  * kzgmi_fr_ntt* with the evaluation-form openings kzgmi_open_evals*, and the transforms over G1
- * kzgmi_g1_ntt* with the openings at every point of a domain, kzgmi_open_all_key_* and kzgmi_open_all*.
+ * kzgmi_g1_ntt* with the openings at every point of a domain, kzgmi_open_all_key_* and kzgmi_open_all*,
+ * and the openings on every coset of a domain, kzgmi_open_cosets_key_* and kzgmi_open_cosets*.
  * A caller built
  * against another revision must not bind the library: compare with kzgmi_abi_version(). */
 #define KZGMI_ABI_VERSION 6
@@ -826,6 +827,44 @@ int kzgmi_open_all_device(kzgmi_ctx* ctx, const kzgmi_open_all_key* key, const v
                           void* d_ys_out, void* d_proofs_out);
 int kzgmi_open_all_device_async(kzgmi_ctx* ctx, const kzgmi_open_all_key* key, int slot, const void* d_coeffs, size_t m,
                                 uint32_t flags, void* d_ys_out, void* d_proofs_out);
+
+/* ---- KZG openings on every coset of a domain (FK20 multi-proofs) -- both curves, any
+ * power-of-two shape.  N = 2^logN is the coefficient capacity, l = 2^logl the coset size, K = 2^logk the
+ * number of cosets, n = K l, R = N / l; w_n is the root of the kzgmi_fr_ntt section.  For
+ * p = sum_{i<m} c_i X^i with m <= N (read as zero above m) and every coset e < K:
+ *   h_e = w_n^e,  z_e = h_e^l,  coset e = { h_e w_l^j : j < l },  w_l = w_n^K
+ *   ys[e][j] = p(w_n^(e + K j)),   proofs[e] = [q_e(tau)]_1,  q_e = floor(p / (X^l - z_e))
+ * -- the proof that p agrees on coset e with I_e = p mod (X^l - z_e), checked by
+ * e(proof_e, [tau^l - z_e]_2) = e(C - [I_e(tau)]_1, [1]_2).  With l = 1 the results are kzgmi_open_all's,
+ * with l = N every proof is the point at infinity.  The outputs are coset-major: count x K uncompressed G1
+ * encodings and count x K l x 32 B big-endian evaluations, polynomial t's coset e at entry t K + e and its
+ * evaluation j at value (t K + e) l + j.  flags = KZGMI_NTT_BITREV puts coset rev_logk(i) at proof index i
+ * and p(w_n^rev(k)), rev over logk + logl bits, at value k of a polynomial -- on BLS12-381 at
+ * (logN, logl, logk) = (12, 6, 7) exactly the cell and proof order of EIP-7594.  No other flag is accepted.
+ * ys_out may be NULL (proofs only).  Polynomial t of the count is at byte 32 m t of coeffs.
+ * The key (kzgmi_open_cosets_key_load) belongs to one commit key's curve and one (logN, logl),
+ * logl <= logN <= 19, whatever logk a call takes, and needs N - l <= the commit key's n (the highest power
+ * read is tau^(N - l - 1)).  It is derived on the device from the commit key's resident row of powers, lives
+ * on the context's primary device and holds 2N XYZZ records (kzgmi_open_cosets_key_device_bytes: 1.5 MiB at
+ * the EIP-7594 shape); the commit key may be freed afterwards.  Loading runs on slot 0, which must be idle.
+ * Bounds of a call: logk >= logN - logl, count N <= 2^19, count K l <= 2^20; count == 0 succeeds and writes
+ * nothing.  Errors: KZGMI_ERR_SCALAR for a coefficient >= r; KZGMI_ERR_ARG for a bound, a stray flag, a key
+ * of another context, misaligned or overlapping device arrays.  The three forms, the alignment rule, the
+ * completion of the async form and the workspace accounting are those of kzgmi_open_all: a failing call
+ * writes no output and leaves the slot usable.  KZGMI_G1NTT_FORM=thread|wave forces the form of the
+ * products as it does the stages'. */
+typedef struct kzgmi_open_cosets_key kzgmi_open_cosets_key;
+int kzgmi_open_cosets_key_load(kzgmi_ctx* ctx, const kzgmi_ck* ck, unsigned logN, unsigned logl,
+                               kzgmi_open_cosets_key** out);
+void kzgmi_open_cosets_key_free(kzgmi_open_cosets_key* key);
+size_t kzgmi_open_cosets_key_device_bytes(const kzgmi_open_cosets_key* key);
+int kzgmi_open_cosets(kzgmi_ctx* ctx, const kzgmi_open_cosets_key* key, const uint8_t* coeffs, size_t m, size_t count,
+                      unsigned logk, uint32_t flags, uint8_t* ys_out, uint8_t* proofs_out);
+int kzgmi_open_cosets_device(kzgmi_ctx* ctx, const kzgmi_open_cosets_key* key, const void* d_coeffs, size_t m, size_t count,
+                             unsigned logk, uint32_t flags, void* d_ys_out, void* d_proofs_out);
+int kzgmi_open_cosets_device_async(kzgmi_ctx* ctx, const kzgmi_open_cosets_key* key, int slot, const void* d_coeffs,
+                                   size_t m, size_t count, unsigned logk, uint32_t flags, void* d_ys_out,
+                                   void* d_proofs_out);
 
 /* Optimal-ate pairing e(P, Q) for P in G1, Q in G2: 12 Fp values in tower order, big-endian:
  * 576 B (BLS12-381) / 384 B (BN254).  Test/diagnostic utility.  (ABI 2 returned e(P, Q)^3 on

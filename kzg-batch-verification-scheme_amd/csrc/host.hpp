@@ -155,6 +155,7 @@ struct kzgmi_cell_srs;
 struct kzgmi_cell_pk;
 struct kzgmi_blob_pk;
 struct kzgmi_open_all_key;
+struct kzgmi_open_cosets_key;
 
 struct kzgmi_ctx {
   int device = 0;
@@ -242,6 +243,7 @@ struct kzgmi_ctx {
   std::vector<kzgmi_cell_pk*> cell_pk_list;    // live cell proof keys: same
   std::vector<kzgmi_blob_pk*> blob_pk_list;    // live blob proof keys: same
   std::vector<kzgmi_open_all_key*> open_all_key_list;  // live open_all keys (host_g1ntt.hip): same, through open_all_keys_detach
+  std::vector<kzgmi_open_cosets_key*> open_cosets_key_list;  // live open_cosets keys (host_g1ntt.hip): same, by the same call
 };
 
 // prover commit key: rows w = 0..15 of 2^(16 w)-shifted SRS points, [row][point] Montgomery affine
@@ -538,8 +540,8 @@ extern template struct HostNtt<Bn254>;
 int ntt_check_args(int curve, unsigned logn, size_t count, uint32_t flags, const uint8_t* shift32, Seed* shift_out,
                    bool* has_shift);
 
-// ---- host_g1ntt.hip: kzgmi_ctx_destroy's detach of the context's live open_all keys (device memory freed; a
-// later kzgmi_open_all_key_free only deletes the struct)
+// ---- host_g1ntt.hip: kzgmi_ctx_destroy's detach of the context's live open_all and open_cosets keys (device
+// memory freed; a later kzgmi_open_all_key_free or kzgmi_open_cosets_key_free only deletes the struct)
 void open_all_keys_detach(kzgmi_ctx* c);
 
 // ---- host_batch.hip: the chunk digests of kzgmi_fs_chunk_digests_device, enqueued on slot 0's stream (no wait)

@@ -14,6 +14,9 @@ constexpr int G1NTT_FORM_AUTO = 0, G1NTT_FORM_THREAD = 1, G1NTT_FORM_WAVE = 2;  
 constexpr unsigned G1NTT_MAX_LOGN = 20;     // kzgmi_g1_ntt: count * n <= 2^20 points per call
 constexpr unsigned OPEN_ALL_MAX_LOGN = 19;  // kzgmi_open_all: its 2n-point transforms stay within that
 static_assert(OPEN_ALL_MAX_LOGN + 1 <= G1NTT_MAX_LOGN, "open_all's 2n-point transform is a transform the library runs");
+// kzgmi_open_cosets: count * N <= 2^19 coefficients (the call's count * 2N terms and the records of its
+// inverse transforms stay within a G1 transform call) and count * K * l <= 2^20 evaluations
+constexpr unsigned OPEN_COSETS_MAX_LOG_COEFFS = OPEN_ALL_MAX_LOGN, OPEN_COSETS_MAX_LOG_POINTS = G1NTT_MAX_LOGN;
 
 template <class Cv>
 struct Launch {
@@ -180,6 +183,27 @@ struct Launch {
   static void g1ntt_key_x(hipStream_t st, const AF* srs29, const uint8_t* srs_inf, uint32_t logn, XY* x);
   static void g1ntt_shift(hipStream_t st, const XY* ihat, uint32_t logn, XY* d);
   static void g1ntt_pad(hipStream_t st, const uint32_t* coef, uint32_t m, uint32_t lg, uint32_t halvings, uint32_t* a);
+  // ---- FK20 multi-proofs on every coset of a domain, kzgmi_open_cosets (cosets.hpp, launch_cosets.hip)
+  // the key's l vectors x^(b) ([b][i], 2N records) from a commit key's resident row of powers; their staged
+  // transforms xs (bit-reversed order) -> the key as the products read it, [pos][b]
+  static void cosets_key_x(hipStream_t st, const AF* srs29, const uint8_t* srs_inf, uint32_t logN, uint32_t logl, XY* x);
+  static void cosets_key_gather(hipStream_t st, const XY* xs, uint32_t logN, uint32_t logl, XY* out);
+  // a[(t l + b) 2^loglen + u] = c_t[l u + b] / 2^halvings (u < ulim, l u + b < m; else 0), count polynomials of m
+  static void cosets_pad(hipStream_t st, const uint32_t* coef, uint32_t m, uint32_t count, uint32_t logl, uint32_t loglen,
+                         uint32_t ulim, uint32_t halvings, uint32_t* a);
+  // records a launch of cosets_products may write into each of its two buffers
+  static size_t cosets_scratch_records(uint32_t logN, uint32_t logl, uint32_t count, int form);
+  // the scalars in term order: out[(t 2R + pos) l + b] = ahat[(t l + b) 2R + pos], count 2N values of 8 LE words (ahat != out)
+  static void cosets_scal(hipStream_t st, const uint32_t* ahat, uint32_t logN, uint32_t logl, uint32_t count, uint32_t* out);
+  // hhat[t 2R + pos] = sum_b [scal[(t 2R + pos) l + b]] key[pos l + b] for count polynomials: the products
+  // and their sums, in the thread or the wave form (form as g1ntt_stages takes it, decided by the
+  // call's count * 2N terms); a and b: cosets_scratch_records each, distinct.  Returns the one that holds hhat
+  static XY* cosets_products(hipStream_t st, const XY* key, const uint32_t* scal, uint32_t logN, uint32_t logl, uint32_t count,
+                             int form, XY* a, XY* b);
+  // d[t K + j] = H_j (j <= R - 2) or infinity, out of count inverse 2R-point transforms' bit-reversed output
+  static void cosets_shift(hipStream_t st, const XY* ihat, uint32_t logr2, uint32_t logk, uint32_t count, XY* d);
+  // 32-byte values, count x K l: out[t n + e l + j] = y[t n + e + K j] (y != out)
+  static void cosets_ys(hipStream_t st, const void* y, uint32_t logk, uint32_t logl, uint32_t count, void* out);
   // ---- generators (launch_gen.hip)
   static void gen_table(hipStream_t st, XY* base, AF* table);
   static void gen_g1(hipStream_t st, const uint8_t* scalars, uint32_t n, const AF* table, uint8_t* out, uint32_t* err);

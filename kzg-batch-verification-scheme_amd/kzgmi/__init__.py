@@ -109,6 +109,12 @@ def lib():
         "kzgmi_open_all": ([vp, vp, vp, sz, c.c_uint32, vp, vp], c.c_int),
         "kzgmi_open_all_device": ([vp, vp, vp, sz, c.c_uint32, vp, vp], c.c_int),
         "kzgmi_open_all_device_async": ([vp, vp, c.c_int, vp, sz, c.c_uint32, vp, vp], c.c_int),
+        "kzgmi_open_cosets_key_load": ([vp, vp, c.c_uint, c.c_uint, c.POINTER(vp)], c.c_int),
+        "kzgmi_open_cosets_key_free": ([vp], None),
+        "kzgmi_open_cosets_key_device_bytes": ([vp], sz),
+        "kzgmi_open_cosets": ([vp, vp, vp, sz, sz, c.c_uint, c.c_uint32, vp, vp], c.c_int),
+        "kzgmi_open_cosets_device": ([vp, vp, vp, sz, sz, c.c_uint, c.c_uint32, vp, vp], c.c_int),
+        "kzgmi_open_cosets_device_async": ([vp, vp, c.c_int, vp, sz, sz, c.c_uint, c.c_uint32, vp, vp], c.c_int),
         "kzgmi_open_evals": ([vp, vp, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
         "kzgmi_open_evals_device": ([vp, vp, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
         "kzgmi_open_evals_device_async": ([vp, vp, c.c_int, vp, c.c_uint, c.c_uint32, vp, sz, vp, vp], c.c_int),
@@ -262,6 +268,8 @@ def exported_symbols():
         "kzgmi_g1_ntt", "kzgmi_g1_ntt_device", "kzgmi_g1_ntt_device_async",
         "kzgmi_open_all_key_load", "kzgmi_open_all_key_free", "kzgmi_open_all_key_device_bytes",
         "kzgmi_open_all", "kzgmi_open_all_device", "kzgmi_open_all_device_async",
+        "kzgmi_open_cosets_key_load", "kzgmi_open_cosets_key_free", "kzgmi_open_cosets_key_device_bytes",
+        "kzgmi_open_cosets", "kzgmi_open_cosets_device", "kzgmi_open_cosets_device_async",
     ]
 
 
@@ -538,6 +546,28 @@ class OpenAllKey:
         try:
             if self.handle:
                 lib().kzgmi_open_all_key_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class OpenCosetsKey:
+    """Key of open_cosets for one commit key and one shape (2^logN coefficients, cosets of 2^logl points): the
+    transforms of the SRS's l strided columns."""
+    ctx: "Context"
+    curve: str
+    logN: int
+    logl: int
+    handle: ctypes.c_void_p
+
+    @property
+    def device_bytes(self) -> int:
+        return int(lib().kzgmi_open_cosets_key_device_bytes(self.handle))
+
+    def __del__(self):
+        try:
+            if self.handle:
+                lib().kzgmi_open_cosets_key_free(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -1021,6 +1051,63 @@ class Context:
         _check(lib().kzgmi_open_all_device_async(self.handle, key.handle, int(slot), _dptr(coeffs, 32 * m) if m else None,
                                                  int(m), NTT_BITREV if bitrev else 0,
                                                  _dptr(ys_out, 32 * n) if ys_out is not None else None, _dptr(out, gb * n)))
+
+    def load_open_cosets_key(self, ck: CommitKey, logN: int, logl: int) -> OpenCosetsKey:
+        """The key of open_cosets for polynomials of up to 2^logN coefficients opened on cosets of 2^logl
+        points, derived on the device from `ck` (which must hold 2^logN - 2^logl powers)."""
+        h = ctypes.c_void_p()
+        self._order(0)
+        _check(lib().kzgmi_open_cosets_key_load(self.handle, ck.handle, int(logN), int(logl), ctypes.byref(h)))
+        key = OpenCosetsKey()
+        key.ctx, key.curve, key.logN, key.logl, key.handle = self, ck.curve, int(logN), int(logl), h
+        return key
+
+    def open_cosets(self, key: OpenCosetsKey, coeffs, logk: int, m: Optional[int] = None, count: int = 1,
+                    bitrev: bool = False, want_ys: bool = True, ys_out=None, out=None):
+        """FK20 multi-proofs of `count` polynomials of m <= 2^key.logN coefficients each (32 B each, one
+        polynomial after the other) on the K = 2^logk cosets of l = 2^key.logl points of the K l-th roots of
+        unity: (proofs, ys) -- count x K encodings and count x K l evaluations, coset-major (bitrev=True: both
+        in bit-reversed order, EIP-7594's at (12, 6, 7)); ys is None with want_ys=False.  m defaults to the
+        input's length / count.  Device tensors in: device tensors out; host bytes in: bytes out."""
+        gb, logk, count = 2 * FP_BYTES[key.curve], int(logk), int(count)
+        flags = NTT_BITREV if bitrev else 0
+        pb, yb = (gb * count) << logk, (32 * count) << (logk + key.logl)
+        if _is_device_tensor(coeffs):
+            import torch
+            if m is None:
+                m = coeffs.numel() * coeffs.element_size() // 32 // max(1, count)
+            if out is None:
+                out = torch.empty(max(1, pb), dtype=torch.uint8, device=coeffs.device)[:pb]
+            if ys_out is None and want_ys:
+                ys_out = torch.empty(max(1, yb), dtype=torch.uint8, device=coeffs.device)[:yb]
+            self._order(0)
+            _check(lib().kzgmi_open_cosets_device(
+                self.handle, key.handle, _dptr(coeffs, 32 * m * count) if m * count else None, int(m), count, logk, flags,
+                _dptr(ys_out, yb) if ys_out is not None and count else None, _dptr(out, pb) if count else None))
+            return out, ys_out
+        hc = _host_ptr(coeffs)
+        if m is None:
+            m = hc[1] // 32 // max(1, count)
+        if hc[1] < 32 * m * count:
+            raise ValueError("input buffer shorter than count polynomials of m coefficients")
+        pbuf = ctypes.create_string_buffer(max(1, pb))
+        ybuf = ctypes.create_string_buffer(max(1, yb)) if want_ys else None
+        _check(lib().kzgmi_open_cosets(self.handle, key.handle, hc[0] or None, int(m), count, logk, flags,
+                                       ctypes.addressof(ybuf) if want_ys else None, ctypes.addressof(pbuf)))
+        del hc
+        return pbuf.raw[:pb], (ybuf.raw[:yb] if want_ys else None)
+
+    def open_cosets_async(self, key: OpenCosetsKey, slot: int, coeffs, m: int, logk: int, ys_out, out, count: int = 1,
+                          bitrev: bool = False):
+        """Enqueue open_cosets() of device tensors on `slot` (ys_out may be None); wait(slot) completes it
+        (and raises its device-side errors)."""
+        gb, logk, count = 2 * FP_BYTES[key.curve], int(logk), int(count)
+        pb, yb = (gb * count) << logk, (32 * count) << (logk + key.logl)
+        self._order(slot)
+        _check(lib().kzgmi_open_cosets_device_async(
+            self.handle, key.handle, int(slot), _dptr(coeffs, 32 * m * count) if m * count else None, int(m), count, logk,
+            NTT_BITREV if bitrev else 0, _dptr(ys_out, yb) if ys_out is not None and count else None,
+            _dptr(out, pb) if count else None))
 
     # ------------------------------------------------------------------ Fiat-Shamir
     def commit_async(self, ck: CommitKey, slot: int, coeffs, m: int):
@@ -1983,6 +2070,12 @@ def g1_ntt(curve: str, points, logn: Optional[int] = None, count: int = 1, inver
 def open_all(key: OpenAllKey, coeffs, m: Optional[int] = None, bitrev: bool = False, want_ys: bool = True):
     """Context.open_all on the key's context."""
     return key.ctx.open_all(key, coeffs, m, bitrev, want_ys)
+
+
+def open_cosets(key: OpenCosetsKey, coeffs, logk: int, m: Optional[int] = None, count: int = 1, bitrev: bool = False,
+                want_ys: bool = True):
+    """Context.open_cosets on the key's context."""
+    return key.ctx.open_cosets(key, coeffs, logk, m, count, bitrev, want_ys)
 
 
 def msm_g1(curve: str, points, scalars, ctx: Optional[Context] = None) -> bytes:
